@@ -6,15 +6,17 @@ One "step" = one BN254 G1 Pippenger MSM over 2^20 (scalar, point) pairs (BASELIN
 scalars and the Montgomery-form bases already resident in HBM when the timed region starts; the
 result (one affine point) lands in host memory, as the reference's `multiscalar_mul_g1` returns it.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 (launched through torch.distributed.run, one rank per GPU): the MSM is sharded by window
 across ranks (north star), each rank reduces its windows to one partial point, the partials are
 exchanged with an RCCL all_gather over xGMI and summed on the host: strong scaling of one MSM.
 
-Rank 0 prints ONE JSON line (metric, value, roofline, cpu_baseline, ...).  `extra` carries the second half of
-BASELINE.json's metric -- Groth16.prove at 2^20 BN254 constraints (median, own roofline and cpu_baseline, proof bytes
-compared with the committed closed-form proof) -- and the other configs (NTT 2^22, the other three groups' MSMs).
+Rank 0 prints ONE JSON line (metric, value, ms_per_step, roofline, ...).  A plain run does only what the headline needs:
+set-up, W warm-up steps, K timed steps, the closed-form check of the result.  --dump-outputs DIR writes the result of the
+last timed step to DIR/msm_result.npy.  --full adds `cpu_baseline` and `extra`: the second half of BASELINE.json's metric
+-- Groth16.prove at 2^20 BN254 constraints (median, own roofline and cpu_baseline, proof bytes compared with the
+committed closed-form proof) -- and the other configs (NTT 2^22, the other three groups' MSMs).
 """
 
 import argparse
@@ -70,8 +72,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--window-bits", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary numbers reported under 'extra' (N = 1 only): "
+    ap.add_argument("--full", action="store_true", help="beside the headline, also measure the CPU baselines and the secondary "
+                    "numbers reported under 'extra' (each can be left out with --no-cpu-baseline / --no-extra)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the MSM result of the last timed step to DIR/msm_result.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary numbers reported under 'extra': "
                     "fixed-base MSM, NTT 2^22, Groth16 prove 2^20")
     ap.add_argument("--prove-log-n", type=int, default=20)
     ap.add_argument("--precompute", action="store_true", help="plan flag ZK_MSM_PRECOMPUTE (fixed-base table 2^(cw) P_i, shared buckets)")
@@ -87,6 +92,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    cpu_baseline = args.full and not args.no_cpu_baseline
+    extra = args.full and not args.no_extra
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started plainly (`python bench.py --gpus N`, the shape of the driver's N = 1 command): this process becomes the
         # launcher.  It has made no GPU call (torch is not even imported yet) and never will; the N ranks are fresh children
@@ -197,6 +206,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -282,7 +293,7 @@ def main():
                 "total_gpu_plus_tail": round(float(stage[4]), 4),
             },
         }
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_baseline and world == 1:
             from oracle import corc  # checker / CPU baseline only
             t1 = time.perf_counter()
             cpu_res = corc.msm(cid, grp, sc_limbs, bases, threads=1)
@@ -310,7 +321,7 @@ def main():
                 "sample": "the same MSM, one OpenMP thread per window of the restatement (rayon-style window parallelism; not what the "
                           f"default wheel does); the host has {os.cpu_count()} logical cores", "seconds": round(cpu_all, 3),
             }
-        if not args.no_extra and world == 1:
+        if extra and world == 1:
             # The same MSM in steady state.  After idle the GPU needs ~20 back-to-back MSMs (~30 ms of load) to reach the clock it
             # then holds (tools/ramp_probe.py, profiles/r04_ramp_probe.log: 1.70-1.79 ms for steps 2-5, 1.46-1.54 from step 21 on),
             # so the headline above -- `--warmup 5`, then 20 timed steps -- is measured on the ramp.  Reported beside it, never as
@@ -333,7 +344,7 @@ def main():
             line["extra"] = extra_metrics(lib, torch, dev, args, bases, d_scalars, expected)
             line["extra"]["msm_sustained_after_clock_ramp"] = sustained
             line["extra"].update(large_msm_metric(lib, torch, args, dev, None, 0, 1))
-    if not args.no_extra and world > 1:
+    if extra and world > 1:
         # the whole prove split over the ranks by task x window (BASELINE metric, second half); collective on all ranks.  The
         # window-only layout of rounds 1-3 runs beside it for comparison.
         sharded = prove_metric(torch, args, dev if args.backend == "nccl" else None, world)
@@ -350,6 +361,14 @@ def main():
     N.check(lib.zk_msm_plan_destroy(handle))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, point):
+    """the MSM result a caller receives (one affine point as 64-bit limbs, x then y) as DIR/msm_result.npy: float64 of shape
+    (2, 32), one row per coordinate, its little-endian bytes -- exact in float64, and a change of any bit changes a value by >= 1"""
+    os.makedirs(path, exist_ok=True)
+    coords = np.ascontiguousarray(point, dtype="<u8").view(np.uint8).reshape(2, -1)
+    np.save(os.path.join(path, "msm_result.npy"), coords.astype(np.float64))
 
 
 def extra_metrics(lib, torch, dev, args, bases, d_scalars, expected):
