@@ -154,7 +154,8 @@ int zk_spmv_long_dev(int curve, uint64_t n_long, const void* d_long_rows, const 
  * 2n-th root of unity g (g^n = -1) the values of u v interpolate P_lo - P_hi, so h = (w - d) / 2 with d = that interpolant: 3 iNTT(n)
  * + 2 NTT(n) of g^i-scaled coefficients + 1 iNTT(n), the scalings and the point-wise product folded into the transforms' passes
  * (the reference goes through the doubled domain: 2 NTT(2n) + iNTT(2n) + fold; same h).  log_n + 1 must not exceed the field's
- * two-adicity (ZK_ERR_DOMAIN).
+ * two-adicity and log_n must not be negative (ZK_ERR_DOMAIN).  log_n = 0 is one point: u = a, v = b, h[0] = 0, and the
+ * divisibility flag says whether a_0 b_0 == c_0.
  * d_work must hold 4 * 2^log_n elements.  *divisible (host int) is set to 0 when a_i b_i != c_i for some i, i.e. when
  * the division would leave a remainder (the reference raises ValueError there); h is meaningless in that case. */
 int zk_qap_h_dev(int curve, int log_n, void* d_a_u, void* d_b_v, const void* d_c, void* d_h, void* d_work,

@@ -168,7 +168,7 @@ ZK_HD Fp<P> fp_sub_lazy(const Fp<P>& a, const Fp<P>& b) {
 // ---- "relaxed" forms for the MSM inner loop: no range selection, so half the instructions of fp_add / fp_sub.
 // Products tolerate operands well above 2p ((a/p)(b/p) <= R/p), so a difference may stay in (0, (K+2)p). ------
 
-// a - b + K p (K = 2 or 4) with the carries propagated (normalized limbs), for a < 2p and 0 <= b < K p: value in (0, (K+2)p)
+// a - b + K p (K = 2, 4 or 8) with the carries propagated (normalized limbs), for a < 2p and 0 <= b < K p: value in (0, (K+2)p)
 template <class P, int K>
 ZK_HD Fp<P> fp_sub_k(const Fp<P>& a, const Fp<P>& b) {
     static_assert(K == 2 || K == 4 || K == 8, "K p constants exist for K = 2, 4, 8");
@@ -215,7 +215,9 @@ ZK_HD Fp<P> fp_sub_twice_sel4(const Fp<P>& t, const Fp<P>& q) {
     return s;
 }
 
-// a - b + 8p, carry-free with borrow-proof limbs (< 3*2^29), for b < 4p... any normalized b below 8p; one product operand only
+// a - b + 8p, carry-free with borrow-proof limbs (< 3*2^29), for a < 2p and a normalized b < 4p; one product operand only.  The
+// top limb of 8p does not borrow, so b must stay clear of it (b_top < P8_top; b < 4p is): a b just below 8p whose top limb equals
+// P8_top wraps the top limb of the result (tests/test_field_edges.py)
 template <class P>
 ZK_HD Fp<P> fp_sub_lazy8(const Fp<P>& a, const Fp<P>& b) {
     Fp<P> r;

@@ -19,6 +19,7 @@
 #include <vector>
 #include "common.hip.h"
 #include "fr_mem.hip.h"
+#include "ntt_lazy.hip.h"
 
 namespace zkmi {
 
@@ -60,108 +61,7 @@ __global__ void powers_kernel(uint32_t* out, Fp<P> g, uint32_t count) {
     for (int i = 0; i < P::W / 4; ++i) q[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
 }
 
-// ---- lazy-range arithmetic of the butterfly passes ---------------------------------------------------------------
-// A radix-4 step of the passes below used to spend a fifth of its VALU instructions on four range-selecting additions
-// (fp_add: two candidate results carried through one pass, then a select).  Inside a pass the values now live in a wider
-// range instead: every element of the LDS tile is NORMALISED (limbs < 2^29) with value < 9p, sums are formed limb by limb
-// without carries, and only the one output per step that is a sum of sums is brought back -- by ONE estimated multiple of
-// 8p and a signed carry pass.  For a step on (x00, x01, x10, x11), all < 9p:
-//     a0 = x00 + x10, b0 = x01 + x11             limb-wise: limbs < 2^30, value < 18p
-//     a1 = w (x00 - x10 + 18p*), b1 = w' (..)    operand limbs < 3 2^29, value < 27p; product < 2p, normalised
-//     x00' = reduce8(a0 + b0)                    limbs < 2^31, value < 36p  ->  normalised, < 8.7p
-//     x01' = w2 (a0 - b0 + 36p*)                 operand limbs < 5 2^29, value < 54p: columns 9 (5 + 1) 2^58 < 2^64
-//     x10' = normalise(a1 + b1)                  < 4p
-//     x11' = w2 (a1 - b1 + 4p*)                  as before
-// (kp* = k p written with borrow-proof limbs).  A Montgomery product needs (a/p)(b/p) <= R/p = 2^261/p (168 for BN254 Fr,
-// 70.7 for BLS12-381 Fr): the twiddles of the 9-word table are canonical (< p), so 54 * 1 fits both fields.
-// tools/model_lazy_ntt.py replays these steps on integers with the limb and column bounds asserted.
-
-// k p as normalised 29-bit limbs, at compile time
-template <class P>
-struct LimbConst { uint32_t v[P::N]; };
-template <class P>
-constexpr LimbConst<P> times_p(uint32_t k) {
-    LimbConst<P> r{};
-    uint64_t carry = 0;
-    for (int i = 0; i < P::N; ++i) {
-        const uint64_t t = (uint64_t)P::M[i] * k + carry;
-        r.v[i] = i < P::N - 1 ? (uint32_t)(t & LIMB_MASK) : (uint32_t)t;
-        carry = t >> LIMB_BITS;
-    }
-    return r;
-}
-
-// a + b, limb by limb (no carries): the caller accounts for the limb width
-template <class P>
-__device__ __forceinline__ Fp<P> lz_add(const Fp<P>& a, const Fp<P>& b) {
-    Fp<P> r;
-#pragma unroll
-    for (int i = 0; i < P::N; ++i) r.v[i] = a.v[i] + b.v[i];
-    return r;
-}
-
-// a - b + K p with borrow-proof limbs: every limb of K p but the top one borrows 2^BITS from the limb above, so no limb goes
-// negative for b with limbs < 2^BITS and value <= K p / 2.  One operand of a product only.
-template <class P, int K, int BITS>
-__device__ __forceinline__ Fp<P> lz_sub(const Fp<P>& a, const Fp<P>& b) {
-    constexpr LimbConst<P> kp = times_p<P>(K);
-    Fp<P> r;
-#pragma unroll
-    for (int i = 0; i < P::N; ++i) {
-        const uint32_t c = kp.v[i] + (i < P::N - 1 ? (1u << BITS) : 0u) - (i > 0 ? (1u << (BITS - LIMB_BITS)) : 0u);
-        r.v[i] = a.v[i] + c - b.v[i];
-    }
-    return r;
-}
-
-// carry pass: limbs < 2^31 in, normalised limbs out, same value
-template <class P>
-__device__ __forceinline__ Fp<P> lz_norm(const Fp<P>& a) {
-    Fp<P> r;
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < P::N; ++i) {
-        const uint32_t t = a.v[i] + c;
-        if (i < P::N - 1) {
-            r.v[i] = t & LIMB_MASK;
-            c = t >> LIMB_BITS;
-        } else {
-            r.v[i] = t;
-        }
-    }
-    return r;
-}
-
-// a - k U p for the estimate k = floor(top(a) / (top(U p) + 1)) (one multiply-high), then a signed carry pass: limbs < 2^31 and
-// value < 4.5 U p in, normalised limbs and value < 1.09 U p out (k <= 4, so k * limb(U p) < 2^31 and every limb difference
-// fits a signed 32-bit register).  U = 8 inside a pass, U = 2 on the way to a canonical result.
-template <class P, int U>
-__device__ __forceinline__ Fp<P> lz_reduce(const Fp<P>& a) {
-    constexpr int N = P::N;
-    constexpr LimbConst<P> up = times_p<P>(U);
-    constexpr uint32_t MAGIC = (uint32_t)((1ull << 32) / ((uint64_t)up.v[N - 1] + 1));
-    const uint32_t t = a.v[N - 1] + (a.v[N - 2] >> LIMB_BITS);
-    const uint32_t k = __umulhi(t, MAGIC);
-    Fp<P> r;
-    int32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int32_t d = (int32_t)(a.v[i] - k * up.v[i]) + c;
-        if (i < N - 1) {
-            r.v[i] = (uint32_t)d & LIMB_MASK;
-            c = d >> LIMB_BITS;
-        } else {
-            r.v[i] = (uint32_t)d;
-        }
-    }
-    return r;
-}
-
-// normalised, value < 9p  ->  canonical: one estimated multiple of 2p, then two conditional subtractions of p
-template <class P>
-__device__ __forceinline__ Fp<P> lz_canonical(const Fp<P>& a) {
-    return fp_reduce_full<P>(fp_reduce_full<P>(lz_reduce<P, 2>(a)));
-}
+// the lazy-range arithmetic of the butterfly passes (lz_add, lz_sub, lz_norm, lz_reduce, lz_canonical) is in ntt_lazy.hip.h
 
 // an element as NINE raw limb words (36 bytes): the twiddle table of the passes and the scratch vectors between two passes
 // keep register form, so that neither side pays the 8-word pack / unpack (78 VALU instructions per radix-4 step for the three
@@ -911,6 +811,7 @@ static void free_uv_events() {
 template <class P>
 static int qap_h_dev_impl(int curve, int log_n, uint32_t* a_u, uint32_t* b_v, const uint32_t* c, uint32_t* h,
                           uint32_t* work, int* divisible, hipStream_t stream, hipEvent_t uv_ready = nullptr) {
+    if (log_n < 0) return fail(ZK_ERR_DOMAIN, "Domain size is negative");
     // the coset generator is the primitive 2n-th root of unity: one level of two-adicity above the domain
     if (log_n + 1 > P::TWO_ADICITY || log_n > 30) return fail(ZK_ERR_DOMAIN, "Domain size is too large");
     const uint64_t n = 1ull << log_n;
@@ -919,11 +820,27 @@ static int qap_h_dev_impl(int curve, int log_n, uint32_t* a_u, uint32_t* b_v, co
     uint32_t* U1 = work + n * P::W;          // u g^i, then u on the coset
     uint32_t* V1 = work + 2 * n * P::W;      // v g^i, then v on the coset
     int* dflag = reinterpret_cast<int*>(work + 3 * n * P::W);
+    auto finish = [&]() -> int {
+        ZK_HIP(hipGetLastError());
+        if (!divisible) return ZK_OK;
+        int flag = 0;
+        ZK_HIP(hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, stream));
+        ZK_HIP(hipStreamSynchronize(stream));
+        *divisible = flag ? 0 : 1;
+        return ZK_OK;
+    };
     QapTabs qt;
     int rc;
-    if ((rc = get_qap_tabs<P>(curve, log_n, &qt, stream))) return rc;
+    if (log_n > 0 && (rc = get_qap_tabs<P>(curve, log_n, &qt, stream))) return rc;
     ZK_HIP(hipMemsetAsync(dflag, 0, sizeof(int), stream));
     hipLaunchKernelGGL(qap_eval_check_kernel<P>, dim3(blocks), dim3(256), 0, stream, n, a_u, b_v, c, dflag);
+    if (log_n == 0) {
+        // one point: u = a and v = b (a size-1 transform is the identity) and u v - w is a constant, so h = 0; the check
+        // above sets the flag when a b != c
+        ZK_HIP(hipMemsetAsync(h, 0, P::W * sizeof(uint32_t), stream));
+        if (uv_ready) ZK_HIP(hipEventRecord(uv_ready, stream));
+        return finish();
+    }
     NttPlanFuse<P> f;
     f.k.scale_tab = qt.fwd;
     f.k.out2 = U1;
@@ -949,13 +866,7 @@ static int qap_h_dev_impl(int curve, int log_n, uint32_t* a_u, uint32_t* b_v, co
     fq.k.add_tab = W0;
     fq.dst = h;
     if ((rc = ntt_dev_impl<P>(curve, 1, log_n, U1, stream, &fq))) return rc;
-    ZK_HIP(hipGetLastError());
-    if (!divisible) return ZK_OK;
-    int flag = 0;
-    ZK_HIP(hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, stream));
-    ZK_HIP(hipStreamSynchronize(stream));
-    *divisible = flag ? 0 : 1;
-    return ZK_OK;
+    return finish();
 }
 
 }  // namespace zkmi
