@@ -168,7 +168,7 @@ struct MsmPlan : MsmPlanBase {
         uint32_t *bsums = nullptr, *grand = nullptr, *big_list = nullptr, *big_count = nullptr;
         uint32_t *sorted = nullptr, *partials = nullptr, *buckets = nullptr, *rows = nullptr, *fin = nullptr;
         uint32_t* parts = nullptr;  // partial row / column sums of the two-step strided sums
-        uint32_t *tmp_ref = nullptr, *bin_start = nullptr, *slice_sums = nullptr, *bin_tot = nullptr;  // two-level sort
+        uint32_t *tmp_ref = nullptr, *bin_start = nullptr, *slice_sums = nullptr, *bin_tot = nullptr, *bin_runs = nullptr;  // two-level sort
         uint8_t* tmp_fine = nullptr;  // fine bucket bits of the level-A entries when the reference needs all 31 bits
         // A recorded event costs ~3 us of idle GPU between two kernels (tools/event_gap_probe.hip), so a run records only the four
         // that order work or bound a stage: ev_start (plan), ev_acc0 = sorted (also the lender's "sorted_ready"), ev_acc1 =
@@ -205,7 +205,7 @@ struct MsmPlan : MsmPlanBase {
         // this plan is still in flight
         (void)hipDeviceSynchronize();
         void* bufs[] = {ws.hist, ws.total, ws.bstart, ws.sstart, ws.bsums, ws.grand, ws.big_list, ws.big_count,
-                        ws.sorted, ws.partials, ws.buckets, ws.rows, ws.parts, ws.fin, ws.tmp_ref, ws.tmp_fine, ws.bin_start, ws.slice_sums, ws.bin_tot,
+                        ws.sorted, ws.partials, ws.buckets, ws.rows, ws.parts, ws.fin, ws.tmp_ref, ws.tmp_fine, ws.bin_start, ws.slice_sums, ws.bin_tot, ws.bin_runs,
                         d_scalars, d_dig};
         for (void* q : bufs) dev_free_cached(q);
         pinned_free_cached(h_final);
@@ -323,6 +323,7 @@ struct MsmPlan : MsmPlanBase {
                 ZK_ALLOC(&ws.bin_start, (max_sets * (B >> fine_log_for(n)) + 1) * 4);
                 ZK_ALLOC(&ws.slice_sums, 4096 * BINS_SLICES * 4);
                 ZK_ALLOC(&ws.bin_tot, 4096 * 4);
+                ZK_ALLOC(&ws.bin_runs, max_sets * (B >> fine_log_for(n)) * 4);
             }
             ZK_ALLOC(&ws.partials, max_segs * XW * 4);
             ZK_ALLOC(&ws.buckets, keys * XW * 4);
@@ -448,12 +449,18 @@ struct MsmPlan : MsmPlanBase {
             const int fl = fine_log_for(n);
             const uint32_t NB = B >> fl;
             const uint32_t ch8 = (ch_len + 7) & ~7u;  // the kernels read eight digits per load
-            if (wide) hipLaunchKernelGGL(hist_hi_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), NB * 4, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, l.hist);
-            else hipLaunchKernelGGL(hist_hi_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), NB * 4, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, l.hist);
             // fixed-base mode: one bucket set fed by all (window, chunk) sub-histograms; general mode: one set per window
             const int sets = pre ? 1 : w_count, subs = pre ? w_count * nchunk : nchunk;
             const uint32_t pairs = (uint32_t)sets * NB;
-            if ((uint64_t)pairs * subs >= (1u << 17)) {
+            // general mode with a small count matrix: no scan launch, every level-A workgroup derives its own offsets from
+            // the raw counts and the row totals (kept behind the count matrix in l.hist)
+            const bool derive = !pre && NB <= (uint32_t)SORT_THREADS && (uint64_t)nchunk * NB <= 8192;
+            uint32_t* rowtot = derive ? l.hist + (size_t)w_count * nchunk * NB : nullptr;
+            if (wide) hipLaunchKernelGGL(hist_hi_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), (NB + 1) * 4, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, l.hist, rowtot);
+            else hipLaunchKernelGGL(hist_hi_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), (NB + 1) * 4, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, l.hist, rowtot);
+            if (derive) {
+                // offsets derived in scatter_hi_staged_kernel
+            } else if ((uint64_t)pairs * subs >= (1u << 17)) {
                 const unsigned bb = (pairs + 63) / 64;
                 hipLaunchKernelGGL(bins_partial_kernel, dim3(bb), dim3(1024), 0, st, l.hist, subs, NB, pairs, l.slice_sums, l.bin_tot);
                 hipLaunchKernelGGL(bins_scan_tot_kernel, dim3(1), dim3(1024), 0, st, l.bin_tot, pairs, l.bin_start, l.bstart + n_keys);
@@ -464,13 +471,17 @@ struct MsmPlan : MsmPlanBase {
             {
                 const uint32_t NBP = (NB + 127) & ~127u;
                 const size_t lds_a = (size_t)SCATTER_TILE * 4 + (size_t)NBP * 12 + (size_t)SCATTER_TILE * 2 + (l.tmp_fine ? SCATTER_TILE : 0);
-                if (wide) hipLaunchKernelGGL(scatter_hi_staged_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), lds_a, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.tmp_ref, l.tmp_fine);
-                else hipLaunchKernelGGL(scatter_hi_staged_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), lds_a, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.tmp_ref, (uint8_t*)nullptr);
+                if (wide) hipLaunchKernelGGL(scatter_hi_staged_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), lds_a, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.tmp_ref, l.tmp_fine,
+                                             (const uint32_t*)rowtot, l.bin_start, l.bstart + n_keys);
+                else hipLaunchKernelGGL(scatter_hi_staged_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), lds_a, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.tmp_ref, (uint8_t*)nullptr,
+                                        (const uint32_t*)rowtot, l.bin_start, l.bstart + n_keys);
             }
             // LDS stage of level B: 1.5x the expected entries of a coarse bin, capped at 96 KiB
             uint64_t expect = ((uint64_t)w_count * m) / ((uint64_t)sets * NB);
             uint32_t stage_cap = (uint32_t)std::min<uint64_t>(24576, std::max<uint64_t>(2048, expect + expect / 2));
-            hipLaunchKernelGGL(sort_lo_kernel, dim3(sets * NB), dim3(SORT_LO_THREADS), (size_t)stage_cap * 4, st, l.bin_start, l.tmp_ref, (const uint8_t*)l.tmp_fine, B, fl, stage_cap, l.bstart, l.sorted);
+            hipLaunchKernelGGL(sort_lo_kernel, dim3(sets * NB), dim3(SORT_LO_THREADS), (size_t)stage_cap * 4, st, l.bin_start, l.tmp_ref, (const uint8_t*)l.tmp_fine, B, fl, stage_cap, seg_len, l.bstart, l.sorted, l.bin_runs);
+            // run offsets in one launch from the bins' run totals
+            hipLaunchKernelGGL(runs_offsets_kernel, dim3((n_keys + SCAN_BLOCK - 1) / SCAN_BLOCK), dim3(SCAN_BLOCK), 0, st, l.bstart, n_keys, seg_len, fl, (const uint32_t*)l.bin_runs, l.sstart, l.big_list, l.big_count);
         } else if (ranged) {
             hipLaunchKernelGGL(hist_range_kernel, dim3(w_count * (B >> range_log)), dim3(SORT_THREADS), (4u << range_log), st, d_dig, m, dstride, c, w_first, range_log, l.total);
         } else {
@@ -479,8 +490,8 @@ struct MsmPlan : MsmPlanBase {
         }
         int rc;
         if (!two_level && (rc = exclusive_scan(l.total, n_keys, l.bstart, st))) return rc;
-        {
-            // run offsets: run counts computed on the fly + three-launch scan
+        if (!two_level) {
+            // run offsets of the other sorts: run counts computed on the fly + three-launch scan
             const uint32_t blocks = (n_keys + SCAN_BLOCK - 1) / SCAN_BLOCK;
             hipLaunchKernelGGL(runs_scan_block_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, l.bstart, n_keys, seg_len, l.sstart, l.bsums, l.big_list, l.big_count);
             hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, l.bsums, blocks, l.grand);

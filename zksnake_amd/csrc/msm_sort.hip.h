@@ -367,12 +367,14 @@ __device__ __forceinline__ uint32_t lds_count(uint32_t* counter, uint32_t idx) {
 template <class DIG>
 static __global__ __launch_bounds__(SORT_THREADS) void hist_hi_kernel(const DIG* __restrict__ dig, uint32_t n, uint32_t dstride, int c,
                                                                       int w_first, int nchunk, uint32_t chunk_len, int fine_log,
-                                                                      uint32_t* __restrict__ hist) {
+                                                                      uint32_t* __restrict__ hist, uint32_t* __restrict__ rowtot) {
+    // rowtot != nullptr: also the entry count of every (window, chunk) row (scatter_hi_staged_kernel derives its offsets)
     extern __shared__ uint32_t lds[];
     const uint32_t B = 1u << (c - 1), NB = B >> fine_log;
     const int wl = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
-    for (uint32_t b = threadIdx.x; b < NB; b += SORT_THREADS) lds[b] = 0;
+    for (uint32_t b = threadIdx.x; b <= NB; b += SORT_THREADS) lds[b] = 0;  // lds[NB]: the row total
     __syncthreads();
+    uint32_t mine = 0;
     uint32_t lo = chunk * chunk_len, hi = lo + chunk_len;
     if (hi > n) hi = n;
     const DIG* d = dig + (size_t)(w_first + wl) * dstride;
@@ -383,12 +385,21 @@ static __global__ __launch_bounds__(SORT_THREADS) void hist_hi_kernel(const DIG*
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             int v = (int)dg[k] - (int)B;
-            if (i + k < hi && v != 0) (void)lds_count(lds, ((uint32_t)(v < 0 ? -v : v) - 1) >> fine_log);
+            if (i + k < hi && v != 0) {
+                (void)lds_count(lds, ((uint32_t)(v < 0 ? -v : v) - 1) >> fine_log);
+                ++mine;
+            }
         }
+    }
+    if (rowtot) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(&lds[NB], mine);
     }
     __syncthreads();
     uint32_t* out = hist + (size_t)blockIdx.x * NB;
     for (uint32_t b = threadIdx.x; b < NB; b += SORT_THREADS) out[b] = lds[b];
+    if (rowtot && threadIdx.x == 0) rowtot[blockIdx.x] = lds[NB];
 }
 
 // counts[(set, sub, bin)] -> start offsets in (set, bin, sub) order, in place; bin_start[(set, bin)] (+ the grand
@@ -556,7 +567,9 @@ static __global__ __launch_bounds__(SORT_THREADS) void scatter_hi_staged_kernel(
                                                                                 int w_first, int nchunk, uint32_t chunk_len, int fine_log,
                                                                                 int shared_buckets, uint32_t table_stride, int table_w0,
                                                                                 const uint32_t* __restrict__ offsets,
-                                                                                uint32_t* __restrict__ tmp, uint8_t* __restrict__ tmp_fine) {
+                                                                                uint32_t* __restrict__ tmp, uint8_t* __restrict__ tmp_fine,
+                                                                                const uint32_t* __restrict__ rowtot,
+                                                                                uint32_t* __restrict__ bin_start, uint32_t* __restrict__ total_out) {
     // tmp_fine != nullptr: the reference alone fills the 31 bits below the sign (fixed-base keys above 2^20 points with
     // 20-bit windows: 13 x 2^22 table rows), and the fine bucket bits travel in a byte array beside the entries
     extern __shared__ uint32_t lds[];
@@ -573,17 +586,80 @@ static __global__ __launch_bounds__(SORT_THREADS) void scatter_hi_staged_kernel(
     uint8_t* slot_fine = reinterpret_cast<uint8_t*>(slot_bin + SCATTER_TILE);   // used when split
     const int index_bits = 31 - fine_log;
     const int wl = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
-    const uint32_t* off = offsets + (size_t)blockIdx.x * NB;
-    for (uint32_t b = threadIdx.x; b < NBP; b += SORT_THREADS) {
-        gcur[b] = b < NB ? off[b] : 0u;
-        tcnt[b] = 0;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (rowtot) {
+        // `offsets` holds the raw counts of hist_hi_kernel (one bucket set per window, NB <= SORT_THREADS): this workgroup
+        // derives its start offsets itself instead of a one-workgroup scan launch -- its window's column sums over the
+        // chunks, the entries of the windows before it from the row totals, a scan over the bins.  The chunk-0
+        // workgroups also write the bin offsets that sort_lo_kernel reads.
+        const uint32_t S = SORT_THREADS / NB;  // slices of the chunks per bin (NB is a power of two)
+        const uint32_t slice_len = ((uint32_t)nchunk + S - 1) / S;
+        const uint32_t* h = offsets + (size_t)wl * nchunk * NB;
+        uint32_t* ptot = buf;                  // [S][NB] partial column sums: all chunks / chunks before ours
+        uint32_t* pbef = buf + SORT_THREADS;
+        {
+            const uint32_t b = threadIdx.x % NB, sl = threadIdx.x / NB;
+            const uint32_t ch0 = sl * slice_len, ch1 = min((uint32_t)nchunk, ch0 + slice_len);
+            uint32_t t = 0, bef = 0;
+            for (uint32_t ch = ch0; ch < ch1; ++ch) {
+                const uint32_t v = h[(size_t)ch * NB + b];
+                t += v;
+                bef += ch < (uint32_t)chunk ? v : 0u;
+            }
+            ptot[threadIdx.x] = t;
+            pbef[threadIdx.x] = bef;
+            uint32_t wb = 0;  // entries of the windows before ours
+            for (uint32_t j = threadIdx.x; j < (uint32_t)wl * nchunk; j += SORT_THREADS) wb += rowtot[j];
+#pragma unroll
+            for (int dd = 32; dd >= 1; dd >>= 1) wb += __shfl_xor(wb, dd, 64);
+            if (lane == 0) wave_tot[wave] = wb;
+        }
+        __syncthreads();
+        uint32_t base = 0;
+        for (uint32_t w2 = 0; w2 < SORT_THREADS / 64; ++w2) base += wave_tot[w2];
+        uint32_t tot = 0, bef = 0;
+        if (threadIdx.x < NB) {
+            for (uint32_t sl = 0; sl < S; ++sl) {
+                tot += ptot[sl * NB + threadIdx.x];
+                bef += pbef[sl * NB + threadIdx.x];
+            }
+        }
+        uint32_t incl = tot;
+#pragma unroll
+        for (int dd = 1; dd < 64; dd <<= 1) {
+            uint32_t o = __shfl_up(incl, dd, 64);
+            if ((int)lane >= dd) incl += o;
+        }
+        __syncthreads();  // wave_tot is reused for the bin scan
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        for (uint32_t w2 = 0; w2 < wave; ++w2) base += wave_tot[w2];
+        const uint32_t bstart = base + incl - tot;  // this window's bin `threadIdx.x` starts here
+        if (threadIdx.x < NB) {
+            gcur[threadIdx.x] = bstart + bef;
+            if (chunk == 0) bin_start[(size_t)wl * NB + threadIdx.x] = bstart;
+        }
+        if (chunk == 0 && wl == (int)gridDim.x / nchunk - 1 && threadIdx.x == NB - 1) {
+            bin_start[(size_t)(wl + 1) * NB] = bstart + tot;  // the grand total
+            *total_out = bstart + tot;
+        }
+        for (uint32_t b = threadIdx.x; b < NBP; b += SORT_THREADS) {
+            if (b >= NB) gcur[b] = 0;
+            tcnt[b] = 0;
+        }
+        __syncthreads();  // buf held the partial sums
+    } else {
+        const uint32_t* off = offsets + (size_t)blockIdx.x * NB;
+        for (uint32_t b = threadIdx.x; b < NBP; b += SORT_THREADS) {
+            gcur[b] = b < NB ? off[b] : 0u;
+            tcnt[b] = 0;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     uint32_t lo = chunk * chunk_len, hi = lo + chunk_len;
     if (hi > n) hi = n;
     const DIG* d = dig + (size_t)(w_first + wl) * dstride;
     const uint32_t ref_base = shared_buckets ? (uint32_t)(w_first + wl - table_w0) * table_stride : 0;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (uint32_t base = lo; base < hi; base += SCATTER_TILE) {
         const uint32_t i = base + threadIdx.x * 8;
         uint32_t val[8], rank[8];
@@ -662,10 +738,18 @@ static __global__ __launch_bounds__(SORT_THREADS) void scatter_hi_staged_kernel(
 }
 
 constexpr int SORT_LO_THREADS = 1024;
+constexpr int SORT_LO_REG = 12;  // entries per lane held in registers: bins of up to 12288 entries (1.5x the typical 8192)
 
-static __global__ __launch_bounds__(SORT_LO_THREADS) void sort_lo_kernel(const uint32_t* __restrict__ bin_start, const uint32_t* __restrict__ tmp, const uint8_t* __restrict__ tmp_fine,
-                                                                         uint32_t B, int fine_log, uint32_t stage_cap,
-                                                                         uint32_t* __restrict__ bucket_start, uint32_t* __restrict__ sorted) {
+// run count of a bucket holding the sorted entries [s0, s0 + cnt) (see runs_offsets_kernel)
+__device__ __forceinline__ uint32_t bucket_runs(uint32_t s0, uint32_t cnt, uint32_t seg_len) {
+    return cnt ? 1 + (s0 + cnt - 1) / seg_len - s0 / seg_len : 0;
+}
+
+// bin_runs != nullptr: also the total run count of the bin's buckets (the second level of the run-offset scan)
+static __global__ __launch_bounds__(SORT_LO_THREADS, 8) void sort_lo_kernel(const uint32_t* __restrict__ bin_start, const uint32_t* __restrict__ tmp, const uint8_t* __restrict__ tmp_fine,
+                                                                         uint32_t B, int fine_log, uint32_t stage_cap, uint32_t seg_len,
+                                                                         uint32_t* __restrict__ bucket_start, uint32_t* __restrict__ sorted,
+                                                                         uint32_t* __restrict__ bin_runs) {
     const bool split = tmp_fine != nullptr;  // fine bucket bits beside the entries (see scatter_hi_staged_kernel)
     constexpr uint32_t FINE = 1u << FINE_LOG_MAX;  // counters; the upper ones stay zero when fine_log < FINE_LOG_MAX
     __shared__ uint32_t cnt[FINE];
@@ -677,7 +761,26 @@ static __global__ __launch_bounds__(SORT_LO_THREADS) void sort_lo_kernel(const u
     const uint32_t s0 = bin_start[blockIdx.x], s1 = bin_start[blockIdx.x + 1];
     for (uint32_t f = threadIdx.x; f < FINE; f += SORT_LO_THREADS) cnt[f] = 0;
     __syncthreads();
-    for (uint32_t e = s0 + threadIdx.x; e < s1; e += SORT_LO_THREADS) (void)lds_count(cnt, split ? (uint32_t)tmp_fine[e] : (tmp[e] >> index_bits) & fine_mask);
+    // The placing pass scatters inside the bin's own slice: done in LDS when the slice fits (the typical n / 128
+    // entries), so that HBM/L2 see coalesced stores instead of one 4-byte request per entry -- the scattered form is
+    // bound by the L2 request rate, not by bytes.  A bin of up to SORT_LO_REG entries per lane is read ONCE: the entries
+    // stay in registers with their rank from the counting atomic, and the placing pass needs neither a second read of
+    // `tmp` nor a second round of LDS atomics.
+    const bool in_regs = s1 - s0 <= (uint32_t)SORT_LO_REG * SORT_LO_THREADS && s1 - s0 <= stage_cap;
+    uint32_t ent[SORT_LO_REG], rk[SORT_LO_REG];  // entry; rank | fine << 16
+    if (in_regs) {
+#pragma unroll
+        for (int k = 0; k < SORT_LO_REG; ++k) {
+            const uint32_t e = s0 + threadIdx.x + (uint32_t)k * SORT_LO_THREADS;
+            if (e < s1) {
+                ent[k] = tmp[e];
+                const uint32_t f = split ? (uint32_t)tmp_fine[e] : (ent[k] >> index_bits) & fine_mask;
+                rk[k] = lds_count(cnt, f) | (f << 16);
+            }
+        }
+    } else {
+        for (uint32_t e = s0 + threadIdx.x; e < s1; e += SORT_LO_THREADS) (void)lds_count(cnt, split ? (uint32_t)tmp_fine[e] : (tmp[e] >> index_bits) & fine_mask);
+    }
     __syncthreads();
     if (threadIdx.x < 64) {  // exclusive scan of the 256 counts by one wave: 4 per lane + a shuffle scan
         uint32_t v[4], sum = 0;
@@ -694,18 +797,38 @@ static __global__ __launch_bounds__(SORT_LO_THREADS) void sort_lo_kernel(const u
         }
         uint32_t run = incl - sum;  // offsets relative to the bin's slice
         uint32_t* bs = bucket_start + (size_t)wl * B + ((size_t)bin << fine_log);
+        uint32_t runs = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t f = threadIdx.x * 4 + k;
             cnt[f] = run;
-            if (f <= fine_mask) bs[f] = s0 + run;
+            if (f <= fine_mask) {
+                bs[f] = s0 + run;
+                runs += bucket_runs(s0 + run, v[k], seg_len);
+            }
             run += v[k];
+        }
+        if (bin_runs) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) runs += __shfl_xor(runs, d, 64);
+            if (threadIdx.x == 0) bin_runs[blockIdx.x] = runs;
         }
     }
     __syncthreads();
-    // The placing pass scatters inside the bin's own slice: done in LDS when the slice fits (the typical n / 128
-    // entries), so that HBM/L2 see 16-byte-per-lane coalesced stores instead of one 4-byte request per entry -- the
-    // scattered form is bound by the L2 request rate, not by bytes.
+    if (in_regs) {
+#pragma unroll
+        for (int k = 0; k < SORT_LO_REG; ++k) {
+            const uint32_t e = s0 + threadIdx.x + (uint32_t)k * SORT_LO_THREADS;
+            if (e < s1) {
+                const uint32_t t = ent[k];
+                const uint32_t pos = cnt[rk[k] >> 16] + (rk[k] & 0xFFFFu);
+                stage[pos] = split ? t : (t & 0x80000000u) | (t & ((1u << index_bits) - 1));
+            }
+        }
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < s1 - s0; e += SORT_LO_THREADS) sorted[s0 + e] = stage[e];
+        return;
+    }
     const bool staged = s1 - s0 <= stage_cap;
     for (uint32_t e = s0 + threadIdx.x; e < s1; e += SORT_LO_THREADS) {
         const uint32_t t = tmp[e];
@@ -718,6 +841,47 @@ static __global__ __launch_bounds__(SORT_LO_THREADS) void sort_lo_kernel(const u
         __syncthreads();
         for (uint32_t e = threadIdx.x; e < s1 - s0; e += SORT_LO_THREADS) sorted[s0 + e] = stage[e];
     }
+}
+
+// Run offsets of the two-level sort in ONE launch (instead of runs_scan_block + scan_sums + scan_add): sort_lo_kernel
+// left the run total of every coarse bin in bin_runs, so a workgroup of 1024 keys (whole bins: 2^fine_log <= 1024) finds
+// its base by summing the totals of the bins before it, then scans its own run counts as runs_scan_block_kernel does.
+static __global__ __launch_bounds__(SCAN_BLOCK) void runs_offsets_kernel(const uint32_t* __restrict__ bucket_start, uint32_t n_keys, uint32_t seg_len,
+                                                                         int fine_log, const uint32_t* __restrict__ bin_runs,
+                                                                         uint32_t* __restrict__ out,
+                                                                         uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_count) {
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    __shared__ uint32_t base_sh[SCAN_BLOCK / 64];
+    const uint32_t key = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // base: run totals of the bins before this workgroup's first key
+    {
+        const uint32_t bins_before = (blockIdx.x * SCAN_BLOCK) >> fine_log;
+        uint32_t b = 0;
+        for (uint32_t j = threadIdx.x; j < bins_before; j += SCAN_BLOCK) b += bin_runs[j];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) b += __shfl_xor(b, d, 64);
+        if (lane == 0) base_sh[wave] = b;
+    }
+    uint32_t r = 0;
+    if (key < n_keys) {
+        const uint32_t s0 = bucket_start[key], s1 = bucket_start[key + 1];
+        r = bucket_runs(s0, s1 - s0, seg_len);
+        if (r > COMBINE_WAVE_MAX) big_list[n_keys - 1 - atomicAdd(big_count + 1, 1u)] = key;
+        else if (r > COMBINE_SMALL_MAX) big_list[atomicAdd(big_count, 1u)] = key;
+    }
+    uint32_t incl = r;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        uint32_t o = __shfl_up(incl, d, 64);
+        if ((int)lane >= d) incl += o;
+    }
+    if (lane == 63) sh[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t w2 = 0; w2 < SCAN_BLOCK / 64; ++w2) before += (w2 < wave ? sh[w2] : 0u) + base_sh[w2];
+    if (key < n_keys) out[key] = before + incl - r;  // exclusive
+    if (key == n_keys - 1) out[n_keys] = before + incl;
 }
 
 // ---- 2'/4'. bucket-range partition (general mode) -----------------------------------------------------
