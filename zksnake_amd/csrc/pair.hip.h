@@ -204,6 +204,9 @@ __device__ __forceinline__ HalfPt<F> pair_add(const HalfPt<F>& p, const HalfPt<F
         r.b = pair_sel<T>(odd, t7, t5);
         return r;
     }
+    // Plain ranges (everything below 2p).  NOT instantiated today: FpOps sets RELAXED and Fp2Ops sets RELAXED2, so no group
+    // reaches the code below and no test runs it (tests/test_gpu_msm_reduce_stages.py covers the two branches above only).
+    // It is kept as the readable statement of the formulas; a field facade without a relaxed flag must test it first.
     const T m1 = F::mul(p.a, q.b);   // U1 | S1
     const T m2 = F::mul(q.a, p.b);   // U2 | S2
     const T d = F::sub(m2, m1);      // P  | R
