@@ -283,6 +283,35 @@ int zk_msm_plan_timings(uint64_t handle, float* ms, int cap);
  * Results never depend on them.  ZK_ERR_ARG for unknown names (including the creation-time options ZKMI_SORT_WGS,
  * ZKMI_FINE_LOG, ZKMI_NO_GLV, ZKMI_PRE_C), for values the plan cannot honour and while a run is in flight. */
 int zk_msm_plan_set_option(uint64_t handle, const char* name, int64_t value);
+/* Test aid: a read-only view of the plan's last run -- the device buffers every stage before the bucket reduction left behind
+ * (read them with zk_dev_download; they stay valid and unchanged until the plan's next run or its destruction) and the scalars
+ * that say how to read them.  `out` receives ZK_MSM_VIEW_SLOTS values; ZK_ERR_ARG when cap is smaller or while a run is in
+ * flight (between zk_msm_plan_enqueue* and zk_msm_plan_finish).  With n_keys = groups * B, m = entries per window of the run:
+ *   [0]  d_dig       digits, pw_count rows of `dstride` values from the plan's FIRST window on, uint16 (uint32 when wide);
+ *                    value = signed digit + 2^(c-1); a split-scalar plan stores k1's digit of scalar i at 2i, k2's at 2i + 1
+ *   [1]  d_bases     affine rows in Montgomery form: P_i; (P_i, phi(P_i)) at rows 2i, 2i + 1 of a split-scalar plan;
+ *                    2^(c (pw_first + k)) P_i at row k n + i of a fixed-base plan
+ *   [2]  sorted      bstart[n_keys] entry words (sign << 31 | row of d_bases), grouped by key = set * B + |digit| - 1
+ *   [3]  bstart      n_keys + 1 offsets into sorted         [4]  sstart   n_keys + 1 run offsets (runs of seg_len-aligned segments)
+ *   [5]  big_list    n_keys keys: buckets of 17 .. 2048 runs from the front, of more from the back
+ *   [6]  big_count   the two lengths                         [7]  partials  one XYZZ row per run of every bucket of >= 2 runs
+ *   [8]  buckets     n_keys XYZZ rows (after the run: the bucket sums)
+ *   [9]  n (entries per window the plan was created for)     [10] n_api (points)   [11] c   [12] nwin   [13] B = 2^(c-1)
+ *   [14] glv (split-scalar plan)   [15] pre (fixed-base plan)   [16] wide   [17] pw_first   [18] pw_count
+ *   [19] w_first, [20] w_count (windows of the last run)     [21] groups (bucket sets)   [22] seg_len   [23] m   [24] dstride
+ *        (slots 19-23 describe the last run whatever it was; after zk_msm_plan_enqueue_shared the entry list that run read is the
+ *        LENDER's: slots 2-6, 24-27 still describe this plan's own last sort)
+ *   [25] sort route (ZK_MSM_ROUTE_*; of the plan's own last sort: a run on a borrowed sort leaves it unchanged)
+ *   [26] fine_log (fine bucket bits of the two-level routes, else 0)   [27] split_fine (fine bits kept beside the entries)
+ *   [28] 1 when the accumulate kernel of the next run would be the lane-pair one (option split_pairs) */
+#define ZK_MSM_VIEW_SLOTS 29
+#define ZK_MSM_ROUTE_NONE 0               /* the plan has not sorted yet */
+#define ZK_MSM_ROUTE_RANGED 1             /* bucket-range partition */
+#define ZK_MSM_ROUTE_ONE_LEVEL 2          /* chunked histogram / prefix / scatter */
+#define ZK_MSM_ROUTE_TWO_LEVEL_DERIVE 3   /* two-level, level-A offsets derived in the scatter kernel */
+#define ZK_MSM_ROUTE_TWO_LEVEL_SCAN 4     /* two-level, one-workgroup scan of the count matrix */
+#define ZK_MSM_ROUTE_TWO_LEVEL_PARTIAL 5  /* two-level, sliced partial sums + scan of the totals + prefix */
+int zk_msm_plan_debug_view(uint64_t handle, uint64_t* out, int cap);
 
 /* ---- single-point host arithmetic (PointG1 / PointG2 methods, src/bn254/curve.rs:25-324) -- */
 

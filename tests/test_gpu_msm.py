@@ -348,6 +348,9 @@ def test_msm_full_size_against_cpu_oracle(gpu, cid, grp, log_n):
             out = np.zeros(PW, dtype=np.uint64)
             N.check(gpu.zk_msm_plan_run(h, n, sc.ctypes.data, 0, 0, 0, N.u64p(out), None))
             assert (out == exp).all(), f"flags={flags}"
+            view = np.zeros(N.MSM_VIEW_SLOTS, dtype=np.uint64)
+            N.check(gpu.zk_msm_plan_debug_view(h, N.u64p(view), N.MSM_VIEW_SLOTS))
+            assert int(view[N.MSM_VIEW_ROUTE]) in N.MSM_ROUTES_TWO_LEVEL, f"flags={flags}: sort route {int(view[N.MSM_VIEW_ROUTE])} is not a two-level one"
             cb, nw = N._i(0), N._i(0)
             N.check(gpu.zk_msm_plan_windows(h, cb, nw))
             parts = []

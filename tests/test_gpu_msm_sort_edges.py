@@ -38,8 +38,9 @@ def _ints(limbs):
     return [int.from_bytes(row.tobytes(), "little") for row in limbs]
 
 
-def _run_both_sorts(gpu, bases, sc, windows=None):
-    """the plan's result with the two-level sort and without; `windows`: run as these (first, count) ranges and add up"""
+def _run_both_sorts(gpu, bases, sc, windows=None, routes=None):
+    """the plan's result with the two-level sort and without; `windows`: run as these (first, count) ranges and add up;
+    `routes`: a list that receives (two_level option, sort route of the run) from the plan's debug view"""
     from zksnake_amd.parallel import sum_points
     n = bases.shape[0]
     h = N._u64(0)
@@ -53,6 +54,10 @@ def _run_both_sorts(gpu, bases, sc, windows=None):
                 out = np.zeros(N.point_limbs(CID, GRP), dtype=np.uint64)
                 N.check(gpu.zk_msm_plan_run(h, sc.shape[0], sc.ctypes.data, 0, first, count, N.u64p(out), None))
                 parts.append(out)
+                if routes is not None:
+                    view = np.zeros(N.MSM_VIEW_SLOTS, dtype=np.uint64)
+                    N.check(gpu.zk_msm_plan_debug_view(h, N.u64p(view), N.MSM_VIEW_SLOTS))
+                    routes.append((two_level, int(view[N.MSM_VIEW_ROUTE])))
             outs.append(parts[0] if len(parts) == 1 else sum_points(CID, GRP, parts))
     finally:
         N.check(gpu.zk_msm_plan_destroy(h))
@@ -123,5 +128,10 @@ def test_window_range_runs(gpu, n, world):
     finally:
         N.check(gpu.zk_msm_plan_destroy(h))
     ranges = [rc for rc in window_ranges(nw.value, world) if rc[1] > 0]
-    for out in _run_both_sorts(gpu, bases, sc, ranges):
+    routes = []
+    for out in _run_both_sorts(gpu, bases, sc, ranges, routes):
         assert (out == exp).all()
+    # 2^18 + 1 points in two halves: 64 chunks x 128 bins, small enough for the level-A workgroups to derive their offsets; the
+    # other two shapes have more chunks per window and go through the scan launch
+    want = N.MSM_ROUTE_TWO_LEVEL_DERIVE if (n, world) == ((1 << 18) + 1, 2) else N.MSM_ROUTE_TWO_LEVEL_SCAN
+    assert {r for on, r in routes if on} == {want} and {r for on, r in routes if not on} == {N.MSM_ROUTE_ONE_LEVEL}, routes

@@ -33,6 +33,11 @@ MSM_PRECOMPUTE = 1
 MSM_HIGH_PRIORITY = 2
 MSM_NO_GLV = 4
 STREAM_PLAN = ctypes.c_void_p(-1)  # ZK_STREAM_PLAN: the plan's own stream
+# zk_msm_plan_debug_view (test aid): number of slots, the slot of the sort route and the ZK_MSM_ROUTE_* values
+MSM_VIEW_SLOTS = 29
+MSM_VIEW_ROUTE = 25
+MSM_ROUTE_RANGED, MSM_ROUTE_ONE_LEVEL, MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL = 1, 2, 3, 4, 5
+MSM_ROUTES_TWO_LEVEL = (MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL)
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -98,6 +103,7 @@ SIGNATURES = {
     "zk_msm_plan_entries": (_i, [_u64, ctypes.POINTER(_u64)]),
     "zk_msm_plan_timings": (_i, [_u64, ctypes.POINTER(ctypes.c_float), _i]),
     "zk_msm_plan_set_option": (_i, [_u64, ctypes.c_char_p, ctypes.c_int64]),
+    "zk_msm_plan_debug_view": (_i, [_u64, _u64p, _i]),
     "zk_point_add": (_i, [_i, _i, _u64p, _u64p, _u64p]),
     "zk_point_neg": (_i, [_i, _i, _u64p, _u64p]),
     "zk_point_sum": (_i, [_i, _i, _u64, _u64p, _u64p]),

@@ -141,6 +141,12 @@ int zk_msm_plan_set_option(uint64_t handle, const char* name, int64_t value) {
     return p->set_option(name, value);
 }
 
+int zk_msm_plan_debug_view(uint64_t handle, uint64_t* out, int cap) {
+    MsmPlanBase* p = find_plan(handle);
+    if (!p) return fail(ZK_ERR_ARG, "unknown MSM plan handle");
+    return p->debug_view(out, cap);
+}
+
 int zk_msm_plan_finish(uint64_t handle, uint64_t* out) {
     MsmPlanBase* p = find_plan(handle);
     if (!p) return fail(ZK_ERR_ARG, "unknown MSM plan handle");

@@ -445,8 +445,12 @@ struct MsmPlan : MsmPlanBase {
         // general mode, small inputs: bucket-range partition (measured faster up to 2^18); otherwise the two-level sort
         const bool ranged = !pre && !wide && m < (1u << 19);
         const bool two_level = !ranged && l.tmp_ref != nullptr && opt.two_level_sort;
+        view_route = ranged ? ZK_MSM_ROUTE_RANGED : ZK_MSM_ROUTE_ONE_LEVEL;   // zk_msm_plan_debug_view
+        view_fine_log = 0;
+        view_dstride = dstride;
         if (two_level) {
             const int fl = fine_log_for(n);
+            view_fine_log = fl;
             const uint32_t NB = B >> fl;
             const uint32_t ch8 = (ch_len + 7) & ~7u;  // the kernels read eight digits per load
             // fixed-base mode: one bucket set fed by all (window, chunk) sub-histograms; general mode: one set per window
@@ -458,6 +462,7 @@ struct MsmPlan : MsmPlanBase {
             uint32_t* rowtot = derive ? l.hist + (size_t)w_count * nchunk * NB : nullptr;
             if (wide) hipLaunchKernelGGL(hist_hi_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), (NB + 1) * 4, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, l.hist, rowtot);
             else hipLaunchKernelGGL(hist_hi_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), (NB + 1) * 4, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, l.hist, rowtot);
+            view_route = derive ? ZK_MSM_ROUTE_TWO_LEVEL_DERIVE : (uint64_t)pairs * subs >= (1u << 17) ? ZK_MSM_ROUTE_TWO_LEVEL_PARTIAL : ZK_MSM_ROUTE_TWO_LEVEL_SCAN;
             if (derive) {
                 // offsets derived in scatter_hi_staged_kernel
             } else if ((uint64_t)pairs * subs >= (1u << 17)) {
@@ -631,6 +636,26 @@ struct MsmPlan : MsmPlanBase {
         } else {
             return fail(ZK_ERR_ARG, std::string("unknown or creation-time MSM option: ") + name);
         }
+        return ZK_OK;
+    }
+
+    // what zk_msm_plan_debug_view reports about the last sort of this plan (stage_sort stores it; nothing reads it on the run path)
+    int view_route = ZK_MSM_ROUTE_NONE, view_fine_log = 0;
+    uint32_t view_dstride = 0;
+    int debug_view(uint64_t* out, int cap) override {
+        std::lock_guard<std::mutex> lock(mu);
+        if (q_pending || q_sorted) return fail(ZK_ERR_ARG, "MSM plan has a run in flight: the view is read between runs");
+        if (!out || cap < ZK_MSM_VIEW_SLOTS) return fail(ZK_ERR_ARG, "zk_msm_plan_debug_view needs room for ZK_MSM_VIEW_SLOTS values");
+        bool split_acc = false;
+        if constexpr (AccumulateSplit<G>::ON) split_acc = opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0;
+        const uint64_t v[ZK_MSM_VIEW_SLOTS] = {
+            (uint64_t)(uintptr_t)d_dig, (uint64_t)(uintptr_t)d_bases, (uint64_t)(uintptr_t)ws.sorted, (uint64_t)(uintptr_t)ws.bstart,
+            (uint64_t)(uintptr_t)ws.sstart, (uint64_t)(uintptr_t)ws.big_list, (uint64_t)(uintptr_t)ws.big_count,
+            (uint64_t)(uintptr_t)ws.partials, (uint64_t)(uintptr_t)ws.buckets,
+            n, n_api, (uint64_t)c, (uint64_t)nwin, B, glv ? 1u : 0u, pre ? 1u : 0u, wide ? 1u : 0u, (uint64_t)pw_first, (uint64_t)pw_count,
+            (uint64_t)ws.w_first, (uint64_t)ws.w_count, ws.groups, ws.seg_len, q_m, view_dstride,
+            (uint64_t)view_route, (uint64_t)view_fine_log, (view_route >= ZK_MSM_ROUTE_TWO_LEVEL_DERIVE && ws.tmp_fine) ? 1u : 0u, split_acc ? 1u : 0u};
+        for (int k = 0; k < ZK_MSM_VIEW_SLOTS; ++k) out[k] = v[k];
         return ZK_OK;
     }
 

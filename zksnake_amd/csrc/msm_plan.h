@@ -143,6 +143,7 @@ struct MsmPlanBase {
     // run is in flight
     virtual int set_option(const char* name, int64_t value) = 0;
     virtual int export_sort(SortExport* out) = 0;                        // of the run in flight
+    virtual int debug_view(uint64_t* out, int cap) = 0;                  // zk_msm_plan_debug_view: buffers and scalars of the last run
     virtual int enqueue_shared(MsmPlanBase* lender, hipStream_t stream) = 0;
     // a second plan over the same bases (shared, read-only) with its own workspace and stream: two MSMs against one key
     // in flight together (tau_1 with u and with v in Groth16.prove) without building the fixed-base table twice
