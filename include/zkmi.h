@@ -322,7 +322,10 @@ int zk_point_sum(int curve, int group, uint64_t n, const uint64_t* points, uint6
 int zk_point_mul(int curve, int group, const uint64_t* a, const uint64_t* scalar, uint64_t* out);  /* __mul__ */
 int zk_point_on_curve(int curve, int group, const uint64_t* a);                                    /* 1 / 0 */
 int zk_point_generator(int curve, int group, uint64_t* out);                                       /* g1() / g2() */
-/* to_bytes / from_bytes = ark-serialize compressed (curve.rs:127-146): 32/64 B (BN254), 48/96 B (BLS12-381) */
+/* to_bytes / from_bytes = ark-serialize compressed (curve.rs:127-146): 32/64 B (BN254), 48/96 B (BLS12-381).
+ * Compression takes reduced coordinates: a coordinate of p or above is refused with ZK_ERR_POINT ("point coordinates are
+ * not reduced field elements"), in zk_points_compress too.  A refused call, of either direction and of either form,
+ * leaves the caller's out buffer as it was. */
 int zk_point_compress(int curve, int group, const uint64_t* a, uint8_t* out);
 int zk_point_decompress(int curve, int group, const uint8_t* in, uint64_t* out);
 

@@ -39,6 +39,30 @@ def oracle_bases(cid, grp, n, seed):
     return ks, pts
 
 
+# ---- stage harnesses: one tests/native source built for the device as the library itself is ------------------------------
+def build_device_harness(src, d, env_var=None, timeout=1500):
+    """tests/native/<name>.hip -> <d>/<name>_dev.so through the library's own pipeline (csrc/hipcc_noreassoc.sh with the
+    Makefile's HIPFLAGS_NOARCH, gfx950); env_var, when set in the environment, names an already built one"""
+    import os
+    import subprocess
+    pre = os.environ.get(env_var) if env_var else None
+    if pre:
+        return pre
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zksnake_amd", "csrc")
+    flags = None
+    with open(os.path.join(csrc, "Makefile")) as fh:
+        for line in fh:
+            if line.startswith("HIPFLAGS_NOARCH"):
+                flags = line.split("?=", 1)[1].split()
+    assert flags
+    name = os.path.splitext(os.path.basename(src))[0]
+    obj, so = os.path.join(str(d), name + ".o"), os.path.join(str(d), name + "_dev.so")
+    env = dict(os.environ, ARCH="gfx950", TMPDIR=str(d))
+    subprocess.run(["bash", os.path.join(csrc, "hipcc_noreassoc.sh"), obj, src] + flags, check=True, timeout=timeout, env=env)
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj], check=True, timeout=300)
+    return so
+
+
 # ---- multi-process tests: ranks as spawned children that report through a queue ---------------------------------------
 def rank_entry(worker, rank, q, args):
     """child side: run worker(rank, *args) -> result; the result or the child's traceback goes back through the queue"""

@@ -54,7 +54,6 @@ from oracle import pyref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "field_edges.hip")
-CSRC = os.path.join(ROOT, "zksnake_amd", "csrc")
 B = 29
 MASK = (1 << B) - 1
 
@@ -718,18 +717,8 @@ def test_host_g2_relaxed_step(host):
 # ---- device build --------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def device(tmp_path_factory, gpu):
-    d = tmp_path_factory.mktemp("fe_dev")
-    flags = None
-    with open(os.path.join(CSRC, "Makefile")) as fh:
-        for line in fh:
-            if line.startswith("HIPFLAGS_NOARCH"):
-                flags = line.split("?=", 1)[1].split()
-    assert flags
-    obj, so = str(d / "field_edges.o"), str(d / "field_edges_dev.so")
-    env = dict(os.environ, ARCH="gfx950", TMPDIR=str(d))
-    subprocess.run(["bash", os.path.join(CSRC, "hipcc_noreassoc.sh"), obj, SRC] + flags, check=True, timeout=900, env=env)
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj], check=True, timeout=300)
-    return Harness(so)
+    from helpers import build_device_harness
+    return Harness(build_device_harness(SRC, tmp_path_factory.mktemp("fe_dev"), timeout=900))
 
 
 @pytest.mark.gpu

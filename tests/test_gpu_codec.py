@@ -2,15 +2,25 @@
 per-point encodings (oracle/pyref.py compress / decompress, pinned by the reference's golden points), all four groups,
 with the error behaviour of the reference's from_hex (ark deserialize_compressed) on damaged input."""
 
+import functools
+import random
+
 import numpy as np
 import pytest
 
+import codec_model as M
 from helpers import CURVES, oracle_bases
 from oracle import corc, pyref
 from zksnake_amd import _native as N
 from zksnake_amd._algebra import PointArray
 
 pytestmark = pytest.mark.gpu
+
+# the tests against the integer model (tests/codec_model.py), below the oracle ones
+SIZES = (1, 127, 128, 129, 300)     # one lane; one below, exactly and one above a 128-lane workgroup; three workgroups
+SENTINEL = np.uint64(0xA5A5A5A5A5A5A5A5)
+GROUPS = [(name, cid, grp) for name, cid in CURVES for grp in (1, 2)]
+group_id = lambda v: v if isinstance(v, str) else None  # noqa: E731
 
 
 def _compress(lib, cid, grp, limbs):
@@ -171,3 +181,176 @@ def test_key_sized_round_trip(gpu, name, cid):
             p = corc.limbs_to_points(pts[i:i + 1], cid, grp)[0]
             nb = gpu.zk_point_bytes(cid, grp)
             assert raw[i * nb:(i + 1) * nb] == pyref.compress(cv, grp, p)
+
+
+# ---- every decode branch, validation edge and batch position against the integer model (tests/codec_model.py) ---------------
+def _positions(n, rnd):
+    """first and last lane of the first workgroup, first lane of the second, the last point, a seeded interior point"""
+    return sorted({at for at in (0, 127, 128, n - 1, rnd.randrange(n)) if at < n})
+
+
+@functools.lru_cache(maxsize=None)
+def _fillers(cid, grp):
+    """300 valid points k G from the C++ oracle and their encodings by oracle/pyref.py; shared, so callers copy"""
+    cv = pyref.curve_by_name(CURVES[cid][0])
+    _, bases = oracle_bases(cid, grp, max(SIZES), 23 + grp)
+    enc = b"".join(pyref.compress(cv, grp, p) for p in corc.limbs_to_points(bases, cid, grp))
+    return bases, np.frombuffer(enc, dtype=np.uint8)
+
+
+def _decode_into_sentinel(lib, cid, grp, raw, n):
+    out = np.full((n, N.point_limbs(cid, grp)), SENTINEL, dtype=np.uint64)
+    bad = N._u64(0)
+    rc = lib.zk_points_decompress(cid, grp, n, N.u8p(raw), N.u64p(out), bad)
+    return rc, bad.value, out
+
+
+def _encode_into_sentinel(lib, cid, grp, rows):
+    out = np.full(rows.shape[0] * lib.zk_point_bytes(cid, grp), 0xA5, dtype=np.uint8)
+    bad = N._u64(0)
+    rc = lib.zk_points_compress(cid, grp, rows.shape[0], N.u64p(rows), N.u8p(out), bad)
+    return rc, bad.value, out
+
+
+def _put(raw, nb, at, data):
+    raw[at * nb:(at + 1) * nb] = np.frombuffer(data, dtype=np.uint8)
+
+
+@pytest.mark.parametrize("name,cid,grp", GROUPS, ids=group_id)
+def test_batch_decode_accepts_every_valid_model_case(gpu, name, cid, grp):
+    """each valid case of codec_model.cases at each position of each batch size among valid points (a batch carries one case per
+    position, the cases rotating through the positions from batch to batch): the model's point limb for limb, every other row
+    the point it encodes"""
+    cv = pyref.curve_by_name(name)
+    nb = gpu.zk_point_bytes(cid, grp)
+    bases, enc = _fillers(cid, grp)
+    valid = [c for c in M.cases(cv, grp, 1) if c[2] == "CODEC_OK"]
+    rows = corc.points_to_limbs([c[3] for c in valid], cid, grp)
+    rnd = random.Random(31)
+    for n in SIZES:
+        pos = _positions(n, rnd)
+        for b in range(len(valid)):
+            raw, want = enc[:n * nb].copy(), bases[:n].copy()
+            for j, at in enumerate(pos):
+                k = (b + j) % len(valid)
+                _put(raw, nb, at, valid[k][1])
+                want[at] = rows[k]
+            rc, _, out = _decode_into_sentinel(gpu, cid, grp, raw, n)
+            assert rc == 0, (n, b, gpu.zk_last_error())
+            assert (out == want).all(), (n, b, np.flatnonzero((out != want).any(axis=1)))
+
+
+@pytest.mark.parametrize("name,cid,grp", GROUPS, ids=group_id)
+def test_batch_decode_refuses_every_invalid_model_case(gpu, name, cid, grp):
+    """each refused case at each position of each batch size: its index, the message of the model's status (the strings of
+    codec.hip.h as codec_model restates them) and an untouched output buffer"""
+    cv = pyref.curve_by_name(name)
+    nb = gpu.zk_point_bytes(cid, grp)
+    _, enc = _fillers(cid, grp)
+    rnd = random.Random(32)
+    invalid = [c for c in M.cases(cv, grp, 1) if c[2] != "CODEC_OK"]
+    assert invalid
+    for n in SIZES:
+        for at in _positions(n, rnd):
+            for label, data, status, _ in invalid:
+                raw = enc[:n * nb].copy()
+                _put(raw, nb, at, data)
+                rc, bad, out = _decode_into_sentinel(gpu, cid, grp, raw, n)
+                assert rc == N.ZK_ERR_POINT and bad == at and gpu.zk_last_error() == M.MESSAGE[status], \
+                    (label, data.hex(), n, at, rc, bad, gpu.zk_last_error())
+                assert (out == SENTINEL).all(), (label, n, at)
+
+
+@pytest.mark.parametrize("name,cid,grp", GROUPS, ids=group_id)
+def test_batch_decode_reports_the_lowest_index_not_the_lowest_code(gpu, name, cid, grp):
+    """two and three refused points with different statuses, the lower index carrying the numerically larger status code:
+    across workgroups, on either side of a workgroup boundary and inside one workgroup"""
+    cv = pyref.curve_by_name(name)
+    nb = gpu.zk_point_bytes(cid, grp)
+    _, enc = _fillers(cid, grp)
+    by_status = {}
+    for c in M.cases(cv, grp, 1):
+        if c[2] != "CODEC_OK":
+            by_status.setdefault(c[2], c)
+    picks = sorted(by_status.values(), key=lambda c: -M.CODE[c[2]])[:3]
+    assert len(picks) == 3 and M.CODE[picks[0][2]] > M.CODE[picks[1][2]] > M.CODE[picks[2][2]]
+    n = 300
+    for spots in ((10, 140, 270), (127, 128), (200, 299), (3, 100), (0, 127), (128, 129, 130)):
+        raw = enc[:n * nb].copy()
+        for at, c in zip(spots, picks):
+            _put(raw, nb, at, c[1])
+        rc, bad, out = _decode_into_sentinel(gpu, cid, grp, raw, n)
+        assert rc == N.ZK_ERR_POINT and bad == spots[0] and gpu.zk_last_error() == M.MESSAGE[picks[0][2]], (spots, bad, gpu.zk_last_error())
+        assert (out == SENTINEL).all()
+
+
+@pytest.mark.parametrize("name,cid,grp", GROUPS, ids=group_id)
+def test_batch_encode_matches_the_model(gpu, name, cid, grp):
+    """the model's valid points and infinity at each position of each batch size give the model's bytes; -P differs from P in
+    the sign bit alone"""
+    cv = pyref.curve_by_name(name)
+    g = pyref.Group(cv, grp)
+    nb = gpu.zk_point_bytes(cid, grp)
+    bases, enc = _fillers(cid, grp)
+    pts = [c[3] for c in M.cases(cv, grp, 1) if c[2] == "CODEC_OK"]
+    assert None in pts
+    rows = corc.points_to_limbs(pts, cid, grp)
+    rnd = random.Random(33)
+    for n in SIZES:
+        pos = _positions(n, rnd)
+        for b in range(len(pts)):
+            batch, want = bases[:n].copy(), enc[:n * nb].copy()
+            for j, at in enumerate(pos):
+                k = (b + j) % len(pts)
+                batch[at] = rows[k]
+                _put(want, nb, at, M.encode_point(cv, grp, pts[k]))
+            rc, _, out = _encode_into_sentinel(gpu, cid, grp, batch)
+            assert rc == 0 and (out == want).all(), (n, b, gpu.zk_last_error())
+    finite = [p for p in pts if p is not None]
+    rc, _, pos_bytes = _encode_into_sentinel(gpu, cid, grp, corc.points_to_limbs(finite, cid, grp))
+    rc2, _, neg_bytes = _encode_into_sentinel(gpu, cid, grp, corc.points_to_limbs([g.neg(p) for p in finite], cid, grp))
+    assert rc == 0 and rc2 == 0
+    diff = (pos_bytes ^ neg_bytes).reshape(len(finite), nb)
+    want = np.zeros_like(diff)
+    if cid == N.CURVE_BN254:
+        want[:, nb - 1] = 0x80
+    else:
+        want[:, 0] = 0x20
+    assert (diff == want).all()
+
+
+@pytest.mark.parametrize("name,cid,grp", GROUPS, ids=group_id)
+def test_batch_encode_refuses_off_curve_and_unreduced_rows(gpu, name, cid, grp):
+    """an off-curve row, and a row with one coordinate raised by p (x + p or y + p, each component alone; 2 p fits the limbs),
+    at the first and last lane of a workgroup and at the last point: the index, the message, an untouched output buffer.  The
+    x bytes are the caller's words, so x + p accepted would be written with its top bits on the flag bits; the lowest index wins
+    here too, against the status order"""
+    cv = pyref.curve_by_name(name)
+    bases, _ = _fillers(cid, grp)
+    fw = N.point_limbs(cid, grp) // (2 * grp)     # 64-bit limbs per base-field element
+    rnd = random.Random(34)
+
+    def refused(batch, at, status):
+        rc, bad, out = _encode_into_sentinel(gpu, cid, grp, batch)
+        assert rc == N.ZK_ERR_POINT and bad == at and gpu.zk_last_error() == M.MESSAGE[status], (batch.shape[0], at, rc, bad, gpu.zk_last_error())
+        assert (out == 0xA5).all()
+
+    def raised(row, k):
+        row = row.copy()
+        v = N.limbs_to_ints(row[k * fw:(k + 1) * fw].reshape(1, fw))[0] + cv.p
+        row[k * fw:(k + 1) * fw] = N.ints_to_limbs([v], fw)[0]
+        return row
+
+    for n in SIZES:
+        for at in _positions(n, rnd):
+            batch = bases[:n].copy()
+            batch[at, 0] ^= 1
+            refused(batch, at, "CODEC_NOT_ON_CURVE")
+            for k in range(2 * grp):
+                batch = bases[:n].copy()
+                batch[at] = raised(batch[at], k)
+                refused(batch, at, "CODEC_COORD_RANGE")
+    batch = bases.copy()
+    batch[5] = raised(batch[5], 0)      # status 8 at the lower index, status 1 in another workgroup
+    batch[200, 0] ^= 1
+    refused(batch, 5, "CODEC_COORD_RANGE")

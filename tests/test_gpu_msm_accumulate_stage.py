@@ -12,14 +12,13 @@ have a test of their own, which needs the GPU machine too because the harness is
 import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import msm_front_model as FM
 from reduce_model import GROUPS, Pool
-from test_field_edges import CSRC, ROOT
+from test_field_edges import ROOT
 
 SRC = os.path.join(ROOT, "tests", "native", "accumulate_stage.hip")
 pytestmark = pytest.mark.gpu
@@ -63,22 +62,10 @@ class Harness:
 
 
 def build_harness(d):
-    """through the library's own pipeline (hipcc_noreassoc.sh + the Makefile's HIPFLAGS_NOARCH, gfx950), as build_stages of
-    test_gpu_msm_reduce_stages.py; ZKMI_ACC_STAGE_LIB names an already built one"""
-    pre = os.environ.get("ZKMI_ACC_STAGE_LIB")
-    if pre:
-        return pre
-    flags = None
-    with open(os.path.join(CSRC, "Makefile")) as fh:
-        for line in fh:
-            if line.startswith("HIPFLAGS_NOARCH"):
-                flags = line.split("?=", 1)[1].split()
-    assert flags
-    obj, so = str(d / "accumulate_stage.o"), str(d / "accumulate_stage_dev.so")
-    env = dict(os.environ, ARCH="gfx950", TMPDIR=str(d))
-    subprocess.run(["bash", os.path.join(CSRC, "hipcc_noreassoc.sh"), obj, SRC] + flags, check=True, timeout=1500, env=env)
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj], check=True, timeout=300)
-    return so
+    """through the library's own pipeline, as build_stages of test_gpu_msm_reduce_stages.py; ZKMI_ACC_STAGE_LIB names an already
+    built one"""
+    from helpers import build_device_harness
+    return build_device_harness(SRC, d, "ZKMI_ACC_STAGE_LIB")
 
 
 @pytest.fixture(scope="module")

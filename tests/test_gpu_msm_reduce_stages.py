@@ -29,14 +29,13 @@ there).  The model, the index expressions and the profile builders have CPU test
 import ctypes
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import reduce_model as M
 from reduce_model import GROUPS, KINDS, Pool, SumJob
-from test_field_edges import CSRC, ROOT, StepRef, check_step, step_inputs, step_record, unpack_acc
+from test_field_edges import ROOT, StepRef, check_step, step_inputs, step_record, unpack_acc
 
 SRC = os.path.join(ROOT, "tests", "native", "reduce_stages.hip")
 G2_GROUPS = [G for G in GROUPS if G.d == 2]
@@ -200,22 +199,10 @@ class Stages:
 
 
 def build_stages(d):
-    """the harness through the library's own pipeline (hipcc_noreassoc.sh + the Makefile's HIPFLAGS_NOARCH, gfx950), as the
-    device fixture of test_field_edges.py does; ZKMI_STAGES_LIB names an already built one (kernel-variant experiments)"""
-    pre = os.environ.get("ZKMI_STAGES_LIB")
-    if pre:
-        return pre
-    flags = None
-    with open(os.path.join(CSRC, "Makefile")) as fh:
-        for line in fh:
-            if line.startswith("HIPFLAGS_NOARCH"):
-                flags = line.split("?=", 1)[1].split()
-    assert flags
-    obj, so = str(d / "reduce_stages.o"), str(d / "reduce_stages_dev.so")
-    env = dict(os.environ, ARCH="gfx950", TMPDIR=str(d))
-    subprocess.run(["bash", os.path.join(CSRC, "hipcc_noreassoc.sh"), obj, SRC] + flags, check=True, timeout=1500, env=env)
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj], check=True, timeout=300)
-    return so
+    """the harness through the library's own pipeline, as the device fixture of test_field_edges.py does; ZKMI_STAGES_LIB names an
+    already built one (kernel-variant experiments)"""
+    from helpers import build_device_harness
+    return build_device_harness(SRC, d, "ZKMI_STAGES_LIB")
 
 
 @pytest.fixture(scope="module")

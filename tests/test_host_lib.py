@@ -135,6 +135,46 @@ def test_point_arithmetic_and_codec(lib, name, cid, grp):
     assert lib.zk_point_on_curve(cid, grp, N.u64p(off)) == 0
 
 
+@pytest.mark.parametrize("name,cid", CURVES)
+@pytest.mark.parametrize("grp", [1, 2])
+def test_point_codec_against_the_integer_model(lib, name, cid, grp):
+    """every case of codec_model.cases (each decode branch and validation edge) through the per-point host codec, which runs the
+    routines of the batched kernels: the model's status message and, when accepted, the model's point limb for limb; a refused
+    call leaves the caller's buffer alone; an accepted point compresses back to the bytes it came from"""
+    import codec_model as M
+    cv = R.curve_by_name(name)
+    W, nb = N.point_limbs(cid, grp), lib.zk_point_bytes(cid, grp)
+    sentinel = np.uint64(0xA5A5A5A5A5A5A5A5)
+    for label, data, status, pt in M.cases(cv, grp, 1):
+        out = np.full(W, sentinel, dtype=np.uint64)
+        rc = lib.zk_point_decompress(cid, grp, N.u8p(np.frombuffer(data, dtype=np.uint8).copy()), N.u64p(out))
+        if status != "CODEC_OK":
+            assert rc == N.ZK_ERR_POINT and lib.zk_last_error() == M.MESSAGE[status], (label, data.hex(), rc, lib.zk_last_error())
+            assert (out == sentinel).all(), (label, data.hex())
+            continue
+        assert rc == 0, (label, data.hex(), lib.zk_last_error())
+        assert (out == corc.points_to_limbs([pt], cid, grp)[0]).all(), (label, data.hex())
+        buf = np.full(nb, 0xA5, dtype=np.uint8)
+        N.check(lib.zk_point_compress(cid, grp, N.u64p(out), N.u8p(buf)))
+        assert bytes(buf) == data == M.encode_point(cv, grp, pt), label
+    # compression takes reduced coordinates: x + p, y + p (one component at a time) and p itself are refused; so is an off-curve
+    # point; a refused call leaves the caller's bytes alone
+    g = R.Group(cv, grp)
+    P = g.mul(g.gen, 5)
+    flat = [P[0], P[1]] if grp == 1 else [*P[0], *P[1]]
+    for k in range(len(flat)):
+        for v in (flat[k] + cv.p, cv.p):
+            row = np.array(N.ints_to_limbs(flat[:k] + [v] + flat[k + 1:], W // len(flat)), dtype=np.uint64).reshape(-1)
+            buf = np.full(nb, 0xA5, dtype=np.uint8)
+            assert lib.zk_point_compress(cid, grp, N.u64p(row), N.u8p(buf)) == N.ZK_ERR_POINT
+            assert lib.zk_last_error() == M.MESSAGE["CODEC_COORD_RANGE"] and (buf == 0xA5).all()
+    row = corc.points_to_limbs([P], cid, grp)[0].copy()
+    row[0] ^= 1
+    buf = np.full(nb, 0xA5, dtype=np.uint8)
+    assert lib.zk_point_compress(cid, grp, N.u64p(row), N.u8p(buf)) == N.ZK_ERR_POINT
+    assert lib.zk_last_error() == M.MESSAGE["CODEC_NOT_ON_CURVE"] and (buf == 0xA5).all()
+
+
 def test_golden_encodings(lib):
     import json
     with open(os.path.join(ROOT, "tests", "golden", "oracle_vectors.json")) as f:

@@ -30,6 +30,7 @@ enum CodecStatus {
     CODEC_X_RANGE,
     CODEC_X_NOT_ON_CURVE,
     CODEC_NOT_IN_SUBGROUP,
+    CODEC_COORD_RANGE,       // encode
 };
 
 inline const char* codec_message(int code) {
@@ -41,6 +42,7 @@ inline const char* codec_message(int code) {
         case CODEC_X_RANGE: return "Cannot deserialize point: x is not a field element";
         case CODEC_X_NOT_ON_CURVE: return "Cannot deserialize point: x is not on the curve";
         case CODEC_NOT_IN_SUBGROUP: return "Cannot deserialize point: not in the prime-order subgroup";
+        case CODEC_COORD_RANGE: return "point coordinates are not reduced field elements";
     }
     return "ok";
 }
@@ -130,19 +132,24 @@ struct CodecLayout {
     static constexpr bool SUBGROUP_CHECK = !(G::CURVE == ZK_CURVE_BN254 && G::GROUP == ZK_G1);
 };
 
-// a = canonical affine words (x | y, all zero = infinity) -> out[TOTAL]
+// a = canonical affine words (x | y, all zero = infinity) -> out[TOTAL].  The x bytes are the input words themselves, so a
+// coordinate of p or above is refused: from_canonical would reduce it for the curve check, and the words of x + p would then be
+// written with their top bits on the flag bits (BN254: bit 254 is the infinity flag).  A refused point leaves out[] as it was.
 template <class G>
 ZK_HD int point_encode(const uint32_t* a, uint8_t* out) {
     typedef typename G::F F;
     typedef typename F::Params P;
     typedef CodecLayout<G> L;
+    for (int k = 0; k < 2 * L::COMPS; ++k)
+        if (!canonical_lt_mod<P>(a + k * P::W)) return CODEC_COORD_RANGE;
     Affine<F> p = {F::from_canonical(a), F::from_canonical(a + F::LIMBS)};
+    const bool inf = aff_is_inf<F>(p);
+    if (!inf && !aff_on_curve<F>(p, F::from_canonical(CurveConsts<G>::b()))) return CODEC_NOT_ON_CURVE;
     for (int i = 0; i < L::TOTAL; ++i) out[i] = 0;
-    if (aff_is_inf<F>(p)) {
+    if (inf) {
         if (L::BLS) out[0] = 0xC0; else out[L::TOTAL - 1] = 0x40;
         return CODEC_OK;
     }
-    if (!aff_on_curve<F>(p, F::from_canonical(CurveConsts<G>::b()))) return CODEC_NOT_ON_CURVE;
     bool larger = coord_is_larger(p.y);
     if (L::BLS) {
         for (int k = 0; k < L::COMPS; ++k) words_to_bytes(out + k * L::FB, a + (L::COMPS - 1 - k) * P::W, L::FB, true);
@@ -206,6 +213,7 @@ ZK_HD int point_decode(const uint8_t* in, uint32_t* out) {
     return CODEC_OK;
 }
 
+#if defined(__HIPCC__)
 // ---- batched: one point per lane --------------------------------------------------------------------------------
 // first_error: min over failing points of (index << 8 | code), ~0 when all passed
 template <class G>
@@ -232,5 +240,6 @@ __global__ __launch_bounds__(128) void points_encode_kernel(const uint32_t* __re
 #define ZK_CODEC_INSTANTIATE(G)                                                                            \
     template __global__ void points_decode_kernel<G>(const uint8_t*, uint64_t, uint32_t*, unsigned long long*); \
     template __global__ void points_encode_kernel<G>(const uint32_t*, uint64_t, uint8_t*, unsigned long long*);
+#endif  // __HIPCC__
 
 }  // namespace zkmi
