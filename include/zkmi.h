@@ -378,6 +378,54 @@ int zk_poly_div_linear_dev(int curve, uint64_t n, const void* d_coeffs, const ui
 int zk_plonk_quotient_dev(int curve, uint64_t m, uint64_t n, const void* const* d_cols, const uint64_t* zh_inv, const uint64_t* beta,
                           const uint64_t* gamma, const uint64_t* alpha, void* d_out, void* stream);
 
+/* ---- multilinear polynomials and the sumcheck prover's round (csrc/mle.hip) --------------------------------------
+ * A polynomial in log_n variables is the table of its 2^log_n evaluations over {0,1}^log_n: canonical Fr elements in device
+ * memory.  Variable 0 is the LEAST significant bit of the table index (ark-poly's order, which GkrPolynomial.to_evaluations
+ * relies on: idx = (c << nb) | b), so fixing variable 0 to r is out[j] = in[2j] + r*(in[2j+1] - in[2j]).  Scalars are canonical
+ * 4-limb integers in host memory, reduced on entry when >= r.  0 <= log_n <= 40.  ZK_ERR_ARG on bad sizes or overlapping
+ * buffers (nothing is written then), ZK_ERR_HIP without a GPU.
+ * ZK_MLE_TILE_LOG: a workgroup holds a tile of 2^ZK_MLE_TILE_LOG contiguous elements in LDS and folds up to that many variables
+ * per launch, so a k-variable fix reads the table ceil(k / ZK_MLE_TILE_LOG) times (each pass on a table 2^ZK_MLE_TILE_LOG times
+ * smaller), not k times. */
+#define ZK_MLE_TILE_LOG 8
+/* Fix variables 0 .. k-1 to r[0 .. k-1] (k * 4 limbs): MultilinearPolynomial.partial_evaluate (src/bn254/mle.rs:86-91,
+ * SparseMultilinearExtension::fix_variables).  d_out receives 2^(log_n - k) elements and must not overlap d_in, which is left
+ * unchanged; k = 0 is a copy, k > log_n is ZK_ERR_ARG.  Enqueues only when k <= ZK_MLE_TILE_LOG; a longer chain keeps its
+ * intermediate tables in library memory and synchronises the stream before it returns. */
+int zk_mle_fix_dev(int curve, int log_n, const void* d_in, int k, const uint64_t* r, void* d_out, void* stream);
+/* out (4 limbs, host) = the sum of the n elements of d_x: sum(mlpoly.to_evaluations()) of sumcheck.py:70,108.  Two levels of
+ * fixed-order partial sums (exact and repeatable); synchronises the stream. */
+int zk_mle_sum_dev(int curve, uint64_t n, const void* d_x, uint64_t* out, void* stream);
+/* out (4 limbs, host) = the polynomial at point[0 .. log_n-1] (point[i] goes to variable i): MultilinearPolynomial.evaluate
+ * (mle.rs:48-57) as a fix of every variable and a one-element download.  d_x is left unchanged.  d_work: device scratch of at
+ * least 2^(max(log_n - ZK_MLE_TILE_LOG, 0) + 1) elements that does not overlap d_x, or NULL to use library memory.
+ * Synchronises the stream. */
+int zk_mle_eval_dev(int curve, int log_n, const void* d_x, const uint64_t* point, uint64_t* out, void* d_work, void* stream);
+/* Evaluations -> monomial coefficients, MultilinearPolynomial.to_coefficients (the recursion ext of mle.rs:9-23): for every
+ * bit b, x[i | 1 << b] -= x[i]; entry i is the coefficient of prod_{b in i} x_b.  ZK_MLE_TILE_LOG bits in the first launch, 6 in
+ * each later one.  d_out == d_in (in place) or no overlap at all. */
+int zk_mle_coeffs_dev(int curve, int log_n, const void* d_in, void* d_out, void* stream);
+/* out[j] = in[i] where bit t of j is bit perm[t] of i (perm: log_n bytes, host): permute_evaluations (mle.rs:59-84), and
+ * swap(a, b, k) (mle.rs:103-107, ark-poly's relabel) with perm = the identity except perm[a+i] = b+i, perm[b+i] = a+i for i < k.
+ * ZK_ERR_ARG unless perm is a permutation of 0 .. log_n-1; d_out must not overlap d_in. */
+int zk_mle_permute_dev(int curve, int log_n, const void* d_in, const uint8_t* perm, void* d_out, void* stream);
+/* One round of the sumcheck prover (sumcheck.py:49-58 _to_univariate inside :77-92 / :115-126; gkr.py:60-80) for
+ *   f(x) = sum_{t < n_terms} term_coeff[t] * prod_{j < term_deg[t]} M_{term_tables[3t + j]}(x),
+ * 1 <= term_deg[t] <= 3 (the reference interpolates the round polynomial on a 4-point domain, sumcheck.py:51, gkr.py:75),
+ * n_terms <= 8, n_tables <= 8, every table over the same log_n variables; a table may appear in several terms or more than once
+ * in one term.  term_coeff: n_terms * 4 limbs; term_tables: n_terms rows of 3 table indices (entries past term_deg[t] ignored).
+ * r == NULL:  s_out (4 * 4 limbs, host) = s(X) = sum over x' in {0,1}^(log_n-1) of f(X, x') at X = 0, 1, 2, 3.
+ * r given (log_n >= 1): variable 0 of every table is first fixed to r, the folded tables (2^(log_n-1) elements each) are written
+ *   to d_tables_out[i], and s_out is s(.) of the FOLDED tables, accumulated in the same pass: a sumcheck round reads each table
+ *   once instead of twice.  The folded tables equal what the fix entry point gives for k = 1.  No d_tables_out[i] may overlap
+ *   an input table or another output.
+ * Tables with no variable left (log_n = 0, or log_n = 1 with r) are constants: s_out is f, four times.
+ * Per-workgroup partial sums are added in a fixed order by a second one-workgroup kernel (exact and repeatable).
+ * Synchronises the stream. */
+int zk_sumcheck_round_dev(int curve, int log_n, int n_tables, const void* const* d_tables, int n_terms, const uint64_t* term_coeff,
+                          const int* term_deg, const int* term_tables, const uint64_t* r, void* const* d_tables_out, uint64_t* s_out,
+                          void* stream);
+
 /* Dense-polynomial helpers over Fr used by the PlonK prover (python/zksnake/plonk/protocol.py:157-484); canonical
  * coefficients, lowest degree first, host memory.  They replace Polynomial.__call__ (src/bn254/polynomial.rs:491-516),
  * Polynomial.__truediv__ by a linear factor (:404-438), the batch_modinv + accumulator loop of protocol.py:296-307 and

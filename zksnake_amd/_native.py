@@ -38,6 +38,7 @@ MSM_VIEW_SLOTS = 29
 MSM_VIEW_ROUTE = 25
 MSM_ROUTE_RANGED, MSM_ROUTE_ONE_LEVEL, MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL = 1, 2, 3, 4, 5
 MSM_ROUTES_TWO_LEVEL = (MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL)
+MLE_TILE_LOG = 8  # ZK_MLE_TILE_LOG: variables one launch of the multilinear kernels folds per 256-element tile
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -125,6 +126,13 @@ SIGNATURES = {
     "zk_poly_div_linear_dev": (_i, [_i, _u64, _vp, _u64p, _vp, _u64p, _vp]),
     "zk_plonk_perm_terms_dev": (_i, [_i, _u64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp, _vp]),
     "zk_plonk_quotient_dev": (_i, [_i, _u64, _u64, ctypes.POINTER(_vp), _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
+    "zk_mle_fix_dev": (_i, [_i, _i, _vp, _i, _u64p, _vp, _vp]),
+    "zk_mle_sum_dev": (_i, [_i, _u64, _vp, _u64p, _vp]),
+    "zk_mle_eval_dev": (_i, [_i, _i, _vp, _u64p, _u64p, _vp, _vp]),
+    "zk_mle_coeffs_dev": (_i, [_i, _i, _vp, _vp, _vp]),
+    "zk_mle_permute_dev": (_i, [_i, _i, _vp, _u8p, _vp, _vp]),
+    "zk_sumcheck_round_dev": (_i, [_i, _i, _i, ctypes.POINTER(_vp), _i, _u64p, ctypes.POINTER(_i), ctypes.POINTER(_i), _u64p,
+                                   ctypes.POINTER(_vp), _u64p, _vp]),
     "zk_fr_poly_eval": (_i, [_i, _u64, _u64p, _u64p, _u64p]),
     "zk_fr_poly_div_linear": (_i, [_i, _u64, _u64p, _u64p, _u64p, _u64p]),
     "zk_fr_grand_product": (_i, [_i, _u64, _u64p, _u64p, _u64p]),

@@ -6,6 +6,7 @@ All transforms and element-wise products run on the GPU through libzkmi.so.
 
 from . import _algebra
 from .constant import BLS12_381_SCALAR_FIELD, BN254_SCALAR_FIELD
+from .mle import MLE_OBJECT
 from .utils import next_power_of_two
 
 POLY_OBJECT = {
@@ -25,6 +26,15 @@ def Polynomial(coeffs, p, domain_size=None):
         terms = [(c, [(v, pw) for v, pw in enumerate(exps) if pw]) for exps, c in coeffs.items()]
         return mod.Polynomial(num_vars, terms, size)
     raise TypeError("Coefficients must be in list or dict")
+
+
+def MultilinearPolynomial(num_vars, sparse_evaluations, p):
+    """multilinear polynomial from the (index, value) pairs of its non-zero evaluations over the boolean hypercube
+    (reference polynomial.py:61-69, including its rule that num_vars == 0 gives zero()); a dense table on the GPU (mle.py)"""
+    cls = MLE_OBJECT[p]
+    if num_vars == 0:
+        return cls.zero()
+    return cls(num_vars, sparse_evaluations)
 
 
 def get_evaluation_point(domain, i, p):
