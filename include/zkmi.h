@@ -68,7 +68,12 @@ int zk_hw_queues_prepare(int* queues /* may be NULL; 0 = runtime default */);
 int zk_init_ex(int device, int* queue_status, int* queues);   /* zk_init + the status above (either pointer may be NULL) */
 /* test aid: one wave that spins for `microseconds` on `stream` (used to observe whether streams overlap) */
 int zk_debug_spin_dev(void* stream, uint64_t microseconds);
-int zk_shutdown(void);              /* free cached twiddle tables and workspaces */
+/* Free what the library caches: twiddle and QAP tables, per-stream scratch and events, every MSM plan and fixed-base table, the
+ * block cache and the pooled streams.  The caller must have no call in flight.  Afterwards: MSM plan handles from before are
+ * refused with ZK_ERR_ARG (handle values are never reused), events of zk_qap_h_dev_begin are invalid, buffers of zk_dev_alloc /
+ * zk_host_alloc and streams of zk_stream_create still belong to the caller and stay valid, and every entry point rebuilds what it
+ * needs on its next call.  Calling it again is a no-op. */
+int zk_shutdown(void);
 int zk_device_count(void);          /* number of visible HIP devices (0 without a GPU; never fails) */
 const char* zk_last_error(void);
 const char* zk_version(void);
@@ -94,6 +99,9 @@ int zk_host_free(void* h_ptr);
 /* HIP streams for callers that keep several device-resident pipelines in flight (the Python host has no HIP binding
  * of its own): non-blocking with respect to the default stream; high_priority != 0 asks for the top priority level. */
 int zk_stream_create(int high_priority, void** stream);
+/* Waits for the work queued on the stream, releases what the library keeps under its handle (the transform scratch vectors,
+ * the event of zk_qap_h_dev_begin / zk_qap_uv_dev: an event handed out for this stream is invalid afterwards) and destroys
+ * it.  NULL is a no-op. */
 int zk_stream_destroy(void* stream);
 int zk_stream_synchronize(void* stream);
 

@@ -18,6 +18,7 @@
 
 extern "C" void zk_ntt_free_cache(void);
 extern "C" void zk_msm_free_all(void);
+extern "C" void zk_ntt_stream_released(void* stream);
 
 namespace zkmi {
 
@@ -491,7 +492,12 @@ int zk_stream_create(int high_priority, void** stream) {
     return ZK_OK;
 }
 int zk_stream_destroy(void* stream) {
-    if (stream) ZK_HIP(hipStreamDestroy((hipStream_t)stream));
+    if (!stream) return ZK_OK;
+    // what the library keeps per stream (NTT scratch vectors, the QAP chain's event) is released with it; work still queued
+    // on the stream may read the scratch, so wait for it first
+    ZK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    zk_ntt_stream_released(stream);
+    ZK_HIP(hipStreamDestroy((hipStream_t)stream));
     return ZK_OK;
 }
 int zk_stream_synchronize(void* stream) {

@@ -1017,4 +1017,31 @@ void zk_ntt_free_cache(void) {
     free_scratch();
 }
 
+// zk_stream_destroy: the scratch vectors and the "u and v are final" event kept for this stream go with it (they used to stay
+// until zk_shutdown, and the next stream that was handed the same handle value inherited them).  The caller has
+// synchronised the stream: nothing queued on it reads the scratch any more.
+void zk_ntt_stream_released(void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    uint32_t* ptr = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mutex);
+        auto it = g_scratch.find(st);
+        if (it != g_scratch.end()) {
+            ptr = it->second.ptr;
+            g_scratch.erase(it);
+        }
+    }
+    if (ptr) (void)hipFree(ptr);
+    hipEvent_t ev = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_uv_mutex);
+        auto it = g_uv_events.find(st);
+        if (it != g_uv_events.end()) {
+            ev = it->second;
+            g_uv_events.erase(it);
+        }
+    }
+    if (ev) (void)hipEventDestroy(ev);
+}
+
 }  // extern "C"
