@@ -39,6 +39,31 @@ def oracle_bases(cid, grp, n, seed):
     return ks, pts
 
 
+def window_range_scalars(cid, grp, vals, c, nwin, glv, first, count):
+    """scalars e_i with sum_i e_i P_i == the partial point of a plan run over the windows [first, first + count): the signed
+    digits of those windows alone, d_w = (bits [cw, cw + c) of s + bias) - 2^(c-1), put back at their places (the integer model
+    of tests/msm_front_model.py); a split-scalar plan cuts the two signed halves, s = k1 + lambda k2 (mod r), and the partial
+    scalar is e(k1) + lambda e(k2).  The expected point is then the CPU oracle's MSM of these scalars."""
+    import msm_front_model as FM
+    import reduce_model as RM
+    G = RM.GROUPS[2 * cid + grp - 1]
+    bias, mask, B = FM.bias_of(c, nwin), (1 << c) - 1, 1 << (c - 1)
+
+    def part(v):
+        t = v + bias
+        assert t >= 0
+        return sum(((((t >> (c * w)) & mask) - B) << (c * w)) for w in range(first, first + count))
+
+    if not glv:
+        return [part(s % G.r) % G.r for s in vals]
+    cs = FM.glv_consts(G)
+    out = []
+    for s in vals:
+        k1, k2 = FM.glv_halves(s % G.r, cs)
+        out.append((part(k1) + cs["lam"] * part(k2)) % G.r)
+    return out
+
+
 # ---- stage harnesses: one tests/native source built for the device as the library itself is ------------------------------
 def build_device_harness(src, d, env_var=None, timeout=1500):
     """tests/native/<name>.hip -> <d>/<name>_dev.so through the library's own pipeline (csrc/hipcc_noreassoc.sh with the
