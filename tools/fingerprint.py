@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = {
     # the accumulate kernel and everything inlined into it
     "msm": ("zksnake_amd/csrc/msm_impl.hip.h", "zksnake_amd/csrc/msm_accumulate.hip.h", "zksnake_amd/csrc/msm_common.hip.h",
-            "zksnake_amd/csrc/msm_sort.hip.h", "zksnake_amd/csrc/msm_reduce.hip.h", "zksnake_amd/csrc/curve.hip.h",
+            "zksnake_amd/csrc/msm_sort.hip.h", "zksnake_amd/csrc/msm_front.h", "zksnake_amd/csrc/msm_front.hip", "zksnake_amd/csrc/msm_reduce.hip.h", "zksnake_amd/csrc/curve.hip.h",
             "zksnake_amd/csrc/field.hip.h", "zksnake_amd/csrc/field_params.h", "zksnake_amd/csrc/msm_plan.h",
             "zksnake_amd/csrc/pair.hip.h", "zksnake_amd/csrc/fp2_split.hip.h", "zksnake_amd/csrc/hipcc_noreassoc.sh", "zksnake_amd/csrc/Makefile"),
 }

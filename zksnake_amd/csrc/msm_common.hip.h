@@ -1,5 +1,5 @@
 // msm_common.hip.h -- device load / store of points, register-form copies and the endomorphism traits shared by the MSM
-// kernel headers (msm_sort.hip.h, msm_accumulate.hip.h, msm_reduce.hip.h) and the plan (msm_impl.hip.h).
+// kernel headers (msm_sort.hip.h, msm_accumulate.hip.h, msm_reduce.hip.h), the front (msm_front.hip) and the plan (msm_impl.hip.h).
 #pragma once
 #include "common.hip.h"
 #include "msm_plan.h"

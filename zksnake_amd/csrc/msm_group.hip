@@ -1,7 +1,7 @@
 // msm_group.hip -- instantiates the MSM kernels and plan for ONE curve group (ZK_GROUP = Bn254G1, ...).
 // Compiled by the Makefile once per group and per part, so that the heavy kernels (field products inlined:
 // a BLS12-381 G2 mixed addition is ~14k instructions) build in parallel:
-//   ZK_PART 0: the plan (host code) and the small kernels; the heavy kernels are only declared (extern template)
+//   ZK_PART 0: the plan (host code only: its kernels are declared extern template, the sort's belong to msm_front.hip)
 //   ZK_PART 1: accumulate / bases_to_mont kernels
 //   ZK_PART 2: combine (3 tiers) / strided_sum / weighted_sum kernels
 //   ZK_PART 3: setup-side kernels (batched normalisation, fixed-base table rows, batch scalar multiplication,

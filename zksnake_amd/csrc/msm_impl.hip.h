@@ -7,7 +7,8 @@
 // group element, returned as its unique affine representative, so any correct bucket method
 // is bit-identical with the reference's.
 //
-// Pipeline (one stream, no host round trip until the tail):
+// Pipeline (one stream, no host round trip until the tail); stages 1-4 do not depend on the group and live in MsmFront
+// (msm_front.h, compiled once in msm_front.hip), stages 5-8 in MsmPlan<G> below:
 //   1. digits      scalar -> signed c-bit window digits (bias trick: s + sum 2^(c-1) 2^(wc),
 //                  then plain bit fields), 2 B per (window, scalar), coalesced.
 //   2. histogram   one workgroup per (window, chunk): 2^(c-1) counters live in LDS (128 KiB at
@@ -36,9 +37,6 @@
 #include "glv_params.h"
 
 #include "msm_common.hip.h"
-#if !defined(ZK_PART) || ZK_PART == 0  // sort-stage kernels and the plan live in part 0 only
-#include "msm_sort.hip.h"
-#endif
 #include "msm_accumulate.hip.h"
 #include "msm_reduce.hip.h"
 
@@ -162,14 +160,10 @@ struct MsmPlan : MsmPlanBase {
     static constexpr int MAX_C = 20;           // widest window (fixed-base plans; digits are then 32-bit)
     bool wide = false;                         // c > 16: 32-bit digits, two-level sort only
 
-    // device workspace of one run (stages 2..7)
+    // device workspace of one run (stages 5..7; the sort's is the front's)
     struct Work {
-        uint32_t *hist = nullptr, *total = nullptr, *bstart = nullptr, *sstart = nullptr;
-        uint32_t *bsums = nullptr, *grand = nullptr, *big_list = nullptr, *big_count = nullptr;
-        uint32_t *sorted = nullptr, *partials = nullptr, *buckets = nullptr, *rows = nullptr, *fin = nullptr;
+        uint32_t *partials = nullptr, *buckets = nullptr, *rows = nullptr, *fin = nullptr;
         uint32_t* parts = nullptr;  // partial row / column sums of the two-step strided sums
-        uint32_t *tmp_ref = nullptr, *bin_start = nullptr, *slice_sums = nullptr, *bin_tot = nullptr, *bin_runs = nullptr;  // two-level sort
-        uint8_t* tmp_fine = nullptr;  // fine bucket bits of the level-A entries when the reference needs all 31 bits
         // A recorded event costs ~3 us of idle GPU between two kernels (tools/event_gap_probe.hip), so a run records only the four
         // that order work or bound a stage: ev_start (plan), ev_acc0 = sorted (also the lender's "sorted_ready"), ev_acc1 =
         // accumulated (the gate of the next plan's accumulate kernel), ev_end (plan); ev_accs only when the accumulate kernel
@@ -190,13 +184,11 @@ struct MsmPlan : MsmPlanBase {
     int pw_first = 0, pw_count = 0;  // windows this plan can run (a sharded rank's share; all of them by default)
     uint32_t B = 0, R = 0, C = 0;
     uint32_t bpr = 0, bpc = 0;       // weighted-sum blocks per row array / per column array
-    int range_log = 0;  // general mode: log2(buckets per sort workgroup)
     Work ws;
+    MsmFront front;  // stages 1-4: scalars -> digits -> sorted entry list
     // shared device buffers
     std::shared_ptr<DeviceBlock> bases_block;  // the (table of) bases: shared by the clones of a plan
     uint32_t* d_bases = nullptr;
-    uint32_t* d_scalars = nullptr;
-    void* d_dig = nullptr;  // windows x (n + 8) digits, uint16_t (c <= 16) or uint32_t
     uint32_t* h_final = nullptr;  // pinned: (S, T) per weighted-sum block
     hipEvent_t ev_start = nullptr, ev_end = nullptr;
 
@@ -204,10 +196,7 @@ struct MsmPlan : MsmPlanBase {
         // blocks go back to the caching allocator, which (unlike hipFree) does not wait for the device: make sure no run of
         // this plan is still in flight
         (void)hipDeviceSynchronize();
-        void* bufs[] = {ws.hist, ws.total, ws.bstart, ws.sstart, ws.bsums, ws.grand, ws.big_list, ws.big_count,
-                        ws.sorted, ws.partials, ws.buckets, ws.rows, ws.parts, ws.fin, ws.tmp_ref, ws.tmp_fine, ws.bin_start, ws.slice_sums, ws.bin_tot, ws.bin_runs,
-                        d_scalars, d_dig};
-        for (void* q : bufs) dev_free_cached(q);
+        for (void* q : {ws.partials, ws.buckets, ws.rows, ws.parts, ws.fin}) dev_free_cached(q);
         pinned_free_cached(h_final);
         for (hipEvent_t e : {ws.ev_acc0, ws.ev_accs, ws.ev_acc1, ws.ev_release, ev_start, ev_end}) if (e) (void)hipEventDestroy(e);
         stream_release((create_flags & ZK_MSM_HIGH_PRIORITY) != 0, own_stream);
@@ -252,15 +241,6 @@ struct MsmPlan : MsmPlanBase {
         if (C > 1024 || R > 1024) return fail(ZK_ERR_ARG, "window too wide for the reduction stage");
         bpr = (R + WS_BLOCK - 1) / WS_BLOCK;
         bpc = (C + WS_BLOCK - 1) / WS_BLOCK;
-        // bucket ranges (general mode, small inputs): about 256 sort workgroups in total, at least 64 buckets each
-        {
-            const uint32_t wgs = opt.sort_workgroups;
-            uint32_t want = std::max<uint32_t>(1u, wgs / (uint32_t)std::max(1, pw_count));
-            uint32_t per = std::max<uint32_t>(64u, B / want);
-            if (per > B) per = B;
-            range_log = log2_u64(per);
-            if ((1u << range_log) > B) range_log = c - 1;
-        }
         const uint64_t entries = (uint64_t)pw_count * n;
         if (entries > 0x7FFFFFFFull) return fail(ZK_ERR_ARG, "MSM too large");
 
@@ -294,9 +274,12 @@ struct MsmPlan : MsmPlanBase {
             }
         }
         mark("stream + bases");
-        ZK_ALLOC(&d_scalars, n_api * FrP::W * 4);
-        ZK_ALLOC(&d_dig, (size_t)pw_count * (n + 8) * (wide ? 4 : 2));
-        if (wide && !two_level_ok()) return fail(ZK_ERR_ARG, "this size does not fit the two-level sort that wide windows need");
+        {
+            FrontLayout fl;
+            fl.c = c; fl.B = B; fl.n = n; fl.n_api = n_api; fl.pre = pre; fl.wide = wide; fl.glv = glv ? &GlvOf<G>::P::K : nullptr;
+            fl.pw_first = pw_first; fl.pw_count = pw_count; fl.nwin = nwin; fl.curve = G::CURVE;
+            ZK_HIP_RC(front.init(fl, &opt));
+        }
         const uint64_t max_sets = pre ? 1ull : (uint64_t)pw_count;
         ZK_HIP_RC(pinned_alloc_cached((void**)&h_final, (size_t)max_sets * (bpr + bpc) * 2 * XW * 4));
         mark("scalars/digits/pinned");
@@ -307,24 +290,7 @@ struct MsmPlan : MsmPlanBase {
             // a window-range run picks its own (shorter) segments: at most SEG_TARGET_LANES of them, or entries / 8
             const uint32_t seg_full = pick_seg_len(entries);
             const uint64_t max_segs = std::max<uint64_t>(entries / seg_full, std::min<uint64_t>(entries / 8, seg_lanes_at_init)) + keys + 8;
-            // windows x chunks <= max(256, windows) sub-histograms: of all B buckets (one-level sort) or of the coarse bins only
-            ZK_ALLOC(&ws.hist, (size_t)std::max<uint64_t>(256, pw_count) * (wide ? (B >> fine_log_for(n)) : B) * 4);
-            ZK_ALLOC(&ws.total, keys * 4);
-            ZK_ALLOC(&ws.bstart, (keys + 1) * 4);
-            ZK_ALLOC(&ws.sstart, (keys + 1) * 4);
-            ZK_ALLOC(&ws.bsums, ((keys + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4);
-            ZK_ALLOC(&ws.grand, 4);
-            ZK_ALLOC(&ws.big_list, keys * 4);
-            ZK_ALLOC(&ws.big_count, 8);
-            ZK_ALLOC(&ws.sorted, entries * 4);
-            if (two_level_ok()) {
-                ZK_ALLOC(&ws.tmp_ref, entries * 4);
-                if (split_fine()) ZK_ALLOC(&ws.tmp_fine, entries);
-                ZK_ALLOC(&ws.bin_start, (max_sets * (B >> fine_log_for(n)) + 1) * 4);
-                ZK_ALLOC(&ws.slice_sums, 4096 * BINS_SLICES * 4);
-                ZK_ALLOC(&ws.bin_tot, 4096 * 4);
-                ZK_ALLOC(&ws.bin_runs, max_sets * (B >> fine_log_for(n)) * 4);
-            }
+            ZK_HIP_RC(front.alloc_workspace());
             ZK_ALLOC(&ws.partials, max_segs * XW * 4);
             ZK_ALLOC(&ws.buckets, keys * XW * 4);
             ZK_ALLOC(&ws.rows, max_sets * (R + C) * XW * 4);
@@ -334,14 +300,7 @@ struct MsmPlan : MsmPlanBase {
         }
         mark("workspace + events");
         // LDS above 64 KiB needs the opt-in
-        int lds_bytes = (int)((wide ? (1u << 15) : B) * 4);  // the one-level kernels never run for wide windows
-        ZK_HIP(hipFuncSetAttribute((const void*)hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        ZK_HIP(hipFuncSetAttribute((const void*)scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        ZK_HIP(hipFuncSetAttribute((const void*)hist_range_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        ZK_HIP(hipFuncSetAttribute((const void*)scatter_range_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        ZK_HIP(hipFuncSetAttribute((const void*)scatter_hi_staged_kernel<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        ZK_HIP(hipFuncSetAttribute((const void*)scatter_hi_staged_kernel<uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 104 * 1024));
-        ZK_HIP(hipFuncSetAttribute((const void*)sort_lo_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
+        ZK_HIP_RC(front.set_kernel_attributes());
         ZK_HIP(hipFuncSetAttribute((const void*)weighted_sum_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)(HalfRegs<F>::COUNT * HS_THREADS * 4)));
         mark("func attributes");
@@ -350,65 +309,10 @@ struct MsmPlan : MsmPlanBase {
         return ZK_OK;
     }
 
-    // chunked sort: windows x chunks workgroups of 1024 threads, ONE per CU (the LDS histogram takes 128 KiB at
-    // c = 16), so their number is kept at or just below the 256 CUs: 272 workgroups would run as 256 + 16,
-    // i.e. take twice as long
-    static int chunks_for(int windows, uint64_t count) {
-        int k = 256 / std::max(1, windows);
-        if (k < 1) k = 1;
-        uint64_t cap = (count + 4095) / 4096;  // at least 4096 entries per chunk
-        if ((uint64_t)k > cap) k = (int)std::max<uint64_t>(1, cap);
-        return k;
-    }
-
-    int exclusive_scan(const uint32_t* in, uint32_t cnt, uint32_t* out, hipStream_t st) {
-        uint32_t blocks = (cnt + SCAN_BLOCK - 1) / SCAN_BLOCK;
-        hipLaunchKernelGGL(scan_block_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, in, cnt, out, ws.bsums);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, ws.bsums, blocks, ws.grand);
-        hipLaunchKernelGGL(scan_add_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, out, cnt, ws.bsums, ws.grand);
-        ZK_HIP(hipGetLastError());
-        return ZK_OK;
-    }
-
-    // fine bucket bits of the two-level sort for n points: the largest of 8, 7 that leaves room for the index in a 32-bit
-    // entry, with at least four coarse bins per window and at most 4096 (window, bin) pairs (one-workgroup scan); 0 = n/a
-    int fine_log_for(uint64_t points) const {
-        // fixed-base mode: ONE bucket set over references into the (window, point) table, so the references are wider
-        // and the coarse bins are shared by all windows -- more, smaller bins keep level B parallel
-        const uint64_t refs = pre ? (uint64_t)pw_count * points : points;
-        const uint64_t sets = pre ? 1 : (uint64_t)pw_count;
-        if (wide) {
-            const int f = c - 13;  // 4096 coarse bins; the fine bits move out of the entry when the reference needs the room
-            return refs <= 0x7FFFFFFFull ? f : 0;
-        }
-        const int f_env = opt.fine_log;  // tuning knob (general mode)
-        if (f_env && !pre && refs <= (1ull << (31 - f_env)) && c - 1 >= f_env + 2 && sets * (B >> f_env) <= 4096) return f_env;
-        const int f_hi = pre ? 5 : FINE_LOG_MAX, f_lo = pre ? 4 : FINE_LOG_MAX - 1;
-        // general mode: the widest bins that still hold about 8192 entries each (one level-B workgroup sorts a bin in LDS;
-        // 2^21 split-scalar entries per window: 7 fine bits, 0.175 ms for digits + sort against 0.20 with 8)
-        int best = 0;
-        for (int f = f_hi; f >= f_lo; --f) {
-            if (!(refs <= (1ull << (31 - f)) && c - 1 >= f + 2 && sets * (B >> f) <= 4096)) continue;
-            if (pre || (points >> (c - 1 - f)) <= 8192) return f;
-            best = f;
-        }
-        return best;
-    }
-
-    // level-A entries carry (sign, fine bucket bits, reference) in 32 bits while that fits; wide windows over a big table
-    // (13 x n rows, n > 2^20) keep the fine bits in a byte array beside them
-    bool split_fine() const {
-        return wide && pre && (uint64_t)pw_count * n > (1ull << (31 - (c - 13)));
-    }
-
     // buckets one lane pair adds up in the first step of the two-step strided sums (0 = one step)
     uint32_t sum_part_len() const {
         const uint32_t k = 16u;
         return (R >= 4 * k && C >= 4 * k) ? k : 0u;
-    }
-
-    bool two_level_ok() const {
-        return opt.two_level_sort && fine_log_for(n) > 0;
     }
 
     // Segment length for a run over `entries` sorted entries: aim at >= 4 waves per SIMD worth of lanes (a window-range
@@ -429,110 +333,27 @@ struct MsmPlan : MsmPlanBase {
         return (uint32_t)sl;
     }
 
-    // ---- the stages of one run, for the windows [ws.w_first, ws.w_first + ws.w_count) on stream st -------------------------
-
-    // stages 2-4: histogram, scans, scatter -> ws.sorted / ws.bstart / ws.sstart (+ the lists of buckets with many runs)
-    int stage_sort(uint32_t m, uint32_t dstride, uint32_t seg_len, hipStream_t st) {
-        Work& l = ws;
-        const int w_first = l.w_first, w_count = l.w_count;
-        const uint32_t n_keys = l.groups * B;
-        const int nchunk = chunks_for(w_count, m);  // this run's windows fill the chip
-        const uint32_t ch_len = (m + nchunk - 1) / nchunk;
-        // digit rows are stored relative to the plan's first window; the kernels index them with absolute windows
-        const uintptr_t dig_base = reinterpret_cast<uintptr_t>(this->d_dig) - (uintptr_t)pw_first * dstride * (wide ? 4 : 2);
-        const uint16_t* d_dig = reinterpret_cast<const uint16_t*>(dig_base);
-        const uint32_t* d_dig32 = reinterpret_cast<const uint32_t*>(dig_base);
-        // general mode, small inputs: bucket-range partition (measured faster up to 2^18); otherwise the two-level sort
-        const bool ranged = !pre && !wide && m < (1u << 19);
-        const bool two_level = !ranged && l.tmp_ref != nullptr && opt.two_level_sort;
-        view_route = ranged ? ZK_MSM_ROUTE_RANGED : ZK_MSM_ROUTE_ONE_LEVEL;   // zk_msm_plan_debug_view
-        view_fine_log = 0;
-        view_dstride = dstride;
-        if (two_level) {
-            const int fl = fine_log_for(n);
-            view_fine_log = fl;
-            const uint32_t NB = B >> fl;
-            const uint32_t ch8 = (ch_len + 7) & ~7u;  // the kernels read eight digits per load
-            // fixed-base mode: one bucket set fed by all (window, chunk) sub-histograms; general mode: one set per window
-            const int sets = pre ? 1 : w_count, subs = pre ? w_count * nchunk : nchunk;
-            const uint32_t pairs = (uint32_t)sets * NB;
-            // general mode with a small count matrix: no scan launch, every level-A workgroup derives its own offsets from
-            // the raw counts and the row totals (kept behind the count matrix in l.hist)
-            const bool derive = !pre && NB <= (uint32_t)SORT_THREADS && (uint64_t)nchunk * NB <= 8192;
-            uint32_t* rowtot = derive ? l.hist + (size_t)w_count * nchunk * NB : nullptr;
-            if (wide) hipLaunchKernelGGL(hist_hi_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), (NB + 1) * 4, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, l.hist, rowtot);
-            else hipLaunchKernelGGL(hist_hi_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), (NB + 1) * 4, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, l.hist, rowtot);
-            view_route = derive ? ZK_MSM_ROUTE_TWO_LEVEL_DERIVE : (uint64_t)pairs * subs >= (1u << 17) ? ZK_MSM_ROUTE_TWO_LEVEL_PARTIAL : ZK_MSM_ROUTE_TWO_LEVEL_SCAN;
-            if (derive) {
-                // offsets derived in scatter_hi_staged_kernel
-            } else if ((uint64_t)pairs * subs >= (1u << 17)) {
-                const unsigned bb = (pairs + 63) / 64;
-                hipLaunchKernelGGL(bins_partial_kernel, dim3(bb), dim3(1024), 0, st, l.hist, subs, NB, pairs, l.slice_sums, l.bin_tot);
-                hipLaunchKernelGGL(bins_scan_tot_kernel, dim3(1), dim3(1024), 0, st, l.bin_tot, pairs, l.bin_start, l.bstart + n_keys);
-                hipLaunchKernelGGL(bins_prefix_kernel, dim3(bb), dim3(1024), 0, st, l.hist, subs, NB, pairs, l.slice_sums, l.bin_start);
-            } else {
-                hipLaunchKernelGGL(bins_scan_kernel, dim3(1), dim3(1024), 0, st, l.hist, sets, subs, NB, l.bin_start, l.bstart + n_keys);
-            }
-            {
-                const uint32_t NBP = (NB + 127) & ~127u;
-                const size_t lds_a = (size_t)SCATTER_TILE * 4 + (size_t)NBP * 12 + (size_t)SCATTER_TILE * 2 + (l.tmp_fine ? SCATTER_TILE : 0);
-                if (wide) hipLaunchKernelGGL(scatter_hi_staged_kernel<uint32_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), lds_a, st, d_dig32, m, dstride, c, w_first, nchunk, ch8, fl, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.tmp_ref, l.tmp_fine,
-                                             (const uint32_t*)rowtot, l.bin_start, l.bstart + n_keys);
-                else hipLaunchKernelGGL(scatter_hi_staged_kernel<uint16_t>, dim3(w_count * nchunk), dim3(SORT_THREADS), lds_a, st, d_dig, m, dstride, c, w_first, nchunk, ch8, fl, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.tmp_ref, (uint8_t*)nullptr,
-                                        (const uint32_t*)rowtot, l.bin_start, l.bstart + n_keys);
-            }
-            // LDS stage of level B: 1.5x the expected entries of a coarse bin, capped at 96 KiB
-            uint64_t expect = ((uint64_t)w_count * m) / ((uint64_t)sets * NB);
-            uint32_t stage_cap = (uint32_t)std::min<uint64_t>(24576, std::max<uint64_t>(2048, expect + expect / 2));
-            hipLaunchKernelGGL(sort_lo_kernel, dim3(sets * NB), dim3(SORT_LO_THREADS), (size_t)stage_cap * 4, st, l.bin_start, l.tmp_ref, (const uint8_t*)l.tmp_fine, B, fl, stage_cap, seg_len, l.bstart, l.sorted, l.bin_runs);
-            // run offsets in one launch from the bins' run totals
-            hipLaunchKernelGGL(runs_offsets_kernel, dim3((n_keys + SCAN_BLOCK - 1) / SCAN_BLOCK), dim3(SCAN_BLOCK), 0, st, l.bstart, n_keys, seg_len, fl, (const uint32_t*)l.bin_runs, l.sstart, l.big_list, l.big_count);
-        } else if (ranged) {
-            hipLaunchKernelGGL(hist_range_kernel, dim3(w_count * (B >> range_log)), dim3(SORT_THREADS), (4u << range_log), st, d_dig, m, dstride, c, w_first, range_log, l.total);
-        } else {
-            hipLaunchKernelGGL(hist_kernel, dim3(w_count * nchunk), dim3(SORT_THREADS), B * 4, st, d_dig, m, dstride, c, w_first, nchunk, ch_len, l.hist);
-            hipLaunchKernelGGL(prefix_kernel, dim3((n_keys + 255) / 256), dim3(256), 0, st, l.hist, pre ? w_count * nchunk : nchunk, B, n_keys, l.total);
-        }
-        int rc;
-        if (!two_level && (rc = exclusive_scan(l.total, n_keys, l.bstart, st))) return rc;
-        if (!two_level) {
-            // run offsets of the other sorts: run counts computed on the fly + three-launch scan
-            const uint32_t blocks = (n_keys + SCAN_BLOCK - 1) / SCAN_BLOCK;
-            hipLaunchKernelGGL(runs_scan_block_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, l.bstart, n_keys, seg_len, l.sstart, l.bsums, l.big_list, l.big_count);
-            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, l.bsums, blocks, l.grand);
-            hipLaunchKernelGGL(scan_add_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, l.sstart, n_keys, l.bsums, l.grand);
-        }
-        if (two_level) {
-            // already sorted
-        } else if (ranged) {
-            hipLaunchKernelGGL(scatter_range_kernel, dim3(w_count * (B >> range_log)), dim3(SORT_THREADS), (4u << range_log), st, d_dig, m, dstride, c, w_first, range_log, l.bstart, l.sorted);
-        } else {
-            const unsigned blocks = pre ? (unsigned)(w_count * nchunk) : (unsigned)(8 * ((w_count + 7) / 8) * nchunk);
-            hipLaunchKernelGGL(scatter_kernel, dim3(blocks), dim3(SORT_THREADS), B * 4, st, d_dig, m, dstride, c, w_first, w_count, nchunk, ch_len, pre ? 1 : 0, (uint32_t)n, pw_first, l.hist, l.bstart, l.sorted);
-        }
-        ZK_HIP(hipGetLastError());
-        return ZK_OK;
-    }
+    // ---- the stages of one run after the front's, for the windows [ws.w_first, ws.w_first + ws.w_count) on stream st -----------
 
     // stage 5: the dominant kernel; stage 6: buckets whose entries span several segments (three tiers, one launch)
-    int stage_accumulate(uint32_t m, uint32_t seg_len, hipStream_t st, const uint32_t* p_sorted, const uint32_t* p_bstart,
-                         const uint32_t* p_sstart, const uint32_t* p_big_list, const uint32_t* p_big_count, bool prio_steps) {
+    int stage_accumulate(uint32_t m, const SortedView& sv, hipStream_t st, bool prio_steps) {
         Work& l = ws;
+        const uint32_t seg_len = sv.seg_len;
         const uint32_t n_keys = l.groups * B;
         const uint64_t lanes_needed = ((uint64_t)l.w_count * m + seg_len - 1) / seg_len;
         bool launched = false;
         if constexpr (AccumulateSplit<G>::ON) {
             if (opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0) {
                 // Fp2 groups: a lane PAIR per segment, every value split by component (fp2_split.hip.h)
-                hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, p_sorted, p_bstart, p_sstart, n_keys, seg_len, prio_steps ? 1u : 0u, l.partials, l.buckets);
+                hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, l.partials, l.buckets);
                 launched = true;
             }
         }
-        if (!launched) hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, p_sorted, p_bstart, p_sstart, n_keys, seg_len, prio_steps ? 1u : 0u, l.partials, l.buckets);
+        if (!launched) hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, l.partials, l.buckets);
         ZK_HIP(hipEventRecord(l.ev_acc1, st));
         const uint32_t small_blocks = (2 * n_keys + COMBINE_THREADS - 1) / COMBINE_THREADS;
         hipLaunchKernelGGL(combine_kernel<G>, dim3(small_blocks + COMBINE_WAVE_BLOCKS + COMBINE_BIG_BLOCKS), dim3(COMBINE_THREADS), 0, st,
-                           l.partials, p_sstart, n_keys, small_blocks, p_big_list, p_big_count, l.buckets);
+                           l.partials, sv.sstart, n_keys, small_blocks, sv.big_list, sv.big_count, l.buckets);
         ZK_HIP(hipGetLastError());
         return ZK_OK;
     }
@@ -585,18 +406,16 @@ struct MsmPlan : MsmPlanBase {
     int run_stages(uint32_t m, uint32_t dstride, hipStream_t st, const SortExport* borrowed = nullptr, int phase = 0, hipEvent_t gate = nullptr) {
         Work& l = ws;
         int rc;
-        const uint32_t seg_len = borrowed ? borrowed->seg_len : (phase == 2 ? l.seg_len : pick_seg_len((uint64_t)l.w_count * m));
+        const uint32_t seg_len = borrowed ? borrowed->view.seg_len : (phase == 2 ? l.seg_len : pick_seg_len((uint64_t)l.w_count * m));
         l.seg_len = seg_len;
-        const uint32_t *p_sorted = l.sorted, *p_bstart = l.bstart, *p_sstart = l.sstart, *p_big_list = l.big_list, *p_big_count = l.big_count;
         if (phase == 2) {
             // sorted in phase 1
         } else if (borrowed) {
-            p_sorted = borrowed->sorted; p_bstart = borrowed->bstart; p_sstart = borrowed->sstart;
-            p_big_list = borrowed->big_list; p_big_count = borrowed->big_count;
             ZK_HIP(hipStreamWaitEvent(st, borrowed->sorted_ready, 0));
-        } else if ((rc = stage_sort(m, dstride, seg_len, st))) {
+        } else if ((rc = front.sort(m, dstride, seg_len, l.w_first, l.w_count, l.groups, st))) {
             return rc;
         }
+        const SortedView sv = borrowed ? borrowed->view : front.view();
         if (phase != 2) ZK_HIP(hipEventRecord(l.ev_acc0, st));
         if (phase == 1) return ZK_OK;
         if (gate) ZK_HIP(hipStreamWaitEvent(st, gate, 0));
@@ -605,7 +424,7 @@ struct MsmPlan : MsmPlanBase {
         // priority steps (msm_accumulate.hip.h) for a run in one piece that waits for nothing: the two-step, gated and shared forms
         // are what a prover uses to overlap several plans
         const bool prio_steps = opt.priority_steps && phase == 0 && !gate && !borrowed;
-        if ((rc = stage_accumulate(m, seg_len, st, p_sorted, p_bstart, p_sstart, p_big_list, p_big_count, prio_steps))) return rc;
+        if ((rc = stage_accumulate(m, sv, st, prio_steps))) return rc;
         if (borrowed) ZK_HIP(hipEventRecord(borrowed->release, st));  // the lender's buffers are no longer read
         return stage_reduce(st);   // the caller records ev_end
     }
@@ -630,7 +449,7 @@ struct MsmPlan : MsmPlanBase {
             if (value == 1 && !AccumulateSplit<G>::ON) return fail(ZK_ERR_ARG, "split_pairs: this group has no pair-split accumulate kernel (base-field groups)");
             opt.split_pairs = (int)value;
         } else if (!strcmp(name, "two_level_sort")) {
-            if (value && !ws.tmp_ref) return fail(ZK_ERR_ARG, "the plan was created without the buffers of the two-level sort");
+            if (value && !front.has_two_level_buffers()) return fail(ZK_ERR_ARG, "the plan was created without the buffers of the two-level sort");
             if (!value && wide) return fail(ZK_ERR_ARG, "windows wider than 16 bits exist in the two-level sort only");
             opt.two_level_sort = value != 0;
         } else {
@@ -639,22 +458,20 @@ struct MsmPlan : MsmPlanBase {
         return ZK_OK;
     }
 
-    // what zk_msm_plan_debug_view reports about the last sort of this plan (stage_sort stores it; nothing reads it on the run path)
-    int view_route = ZK_MSM_ROUTE_NONE, view_fine_log = 0;
-    uint32_t view_dstride = 0;
     int debug_view(uint64_t* out, int cap) override {
         std::lock_guard<std::mutex> lock(mu);
         if (q_pending || q_sorted) return fail(ZK_ERR_ARG, "MSM plan has a run in flight: the view is read between runs");
         if (!out || cap < ZK_MSM_VIEW_SLOTS) return fail(ZK_ERR_ARG, "zk_msm_plan_debug_view needs room for ZK_MSM_VIEW_SLOTS values");
         bool split_acc = false;
         if constexpr (AccumulateSplit<G>::ON) split_acc = opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0;
+        const SortedView own = front.view();
         const uint64_t v[ZK_MSM_VIEW_SLOTS] = {
-            (uint64_t)(uintptr_t)d_dig, (uint64_t)(uintptr_t)d_bases, (uint64_t)(uintptr_t)ws.sorted, (uint64_t)(uintptr_t)ws.bstart,
-            (uint64_t)(uintptr_t)ws.sstart, (uint64_t)(uintptr_t)ws.big_list, (uint64_t)(uintptr_t)ws.big_count,
+            (uint64_t)(uintptr_t)front.digits_buf(), (uint64_t)(uintptr_t)d_bases, (uint64_t)(uintptr_t)own.sorted, (uint64_t)(uintptr_t)own.bstart,
+            (uint64_t)(uintptr_t)own.sstart, (uint64_t)(uintptr_t)own.big_list, (uint64_t)(uintptr_t)own.big_count,
             (uint64_t)(uintptr_t)ws.partials, (uint64_t)(uintptr_t)ws.buckets,
             n, n_api, (uint64_t)c, (uint64_t)nwin, B, glv ? 1u : 0u, pre ? 1u : 0u, wide ? 1u : 0u, (uint64_t)pw_first, (uint64_t)pw_count,
-            (uint64_t)ws.w_first, (uint64_t)ws.w_count, ws.groups, ws.seg_len, q_m, view_dstride,
-            (uint64_t)view_route, (uint64_t)view_fine_log, (view_route >= ZK_MSM_ROUTE_TWO_LEVEL_DERIVE && ws.tmp_fine) ? 1u : 0u, split_acc ? 1u : 0u};
+            (uint64_t)ws.w_first, (uint64_t)ws.w_count, ws.groups, ws.seg_len, q_m, front.view_dstride,
+            (uint64_t)front.view_route, (uint64_t)front.view_fine_log, front.view_split_fine() ? 1u : 0u, split_acc ? 1u : 0u};
         for (int k = 0; k < ZK_MSM_VIEW_SLOTS; ++k) out[k] = v[k];
         return ZK_OK;
     }
@@ -719,32 +536,17 @@ struct MsmPlan : MsmPlanBase {
         if (m > 0) {
             const uint32_t* sc = (const uint32_t*)scalars;
             if (!on_device) {
-                ZK_HIP(hipMemcpyAsync(d_scalars, scalars, (size_t)m_api * FrP::W * 4, hipMemcpyHostToDevice, st));
-                sc = d_scalars;
+                ZK_HIP(hipMemcpyAsync(front.scalars_buf(), scalars, (size_t)m_api * FrP::W * 4, hipMemcpyHostToDevice, st));
+                sc = front.scalars_buf();
             }
             const uint32_t dstride = (m + 7u) & ~7u;
             ZK_HIP(hipEventRecord(ev_start, st));
-            // 1. digits (the windows of this run); digit rows are stored relative to the plan's first window
-            DigitBias bias;
-            memset(&bias, 0, sizeof(bias));
-            for (int w = 0; w < nwin; ++w) {
-                int bit = w * c + (c - 1);
-                bias.v[bit >> 5] |= 1u << (bit & 31);
-            }
-            const uintptr_t dig_base = reinterpret_cast<uintptr_t>(d_dig) - (uintptr_t)pw_first * dstride * (wide ? 4 : 2);
-            if (glv) {
-                if constexpr (GlvOf<G>::OK)
-                    hipLaunchKernelGGL(glv_digits_kernel<FrP>, dim3((m_api + 255) / 256), dim3(256), 0, st, sc, m_api, dstride, c, w_first, w_count, bias,
-                                       GlvOf<G>::P::K, reinterpret_cast<uint16_t*>(dig_base), ws.big_count);
-            } else if (wide) hipLaunchKernelGGL((digits_kernel<FrP, uint32_t>), dim3((m + 255) / 256), dim3(256), 0, st, sc, m, dstride, c, w_first, w_count, bias,
-                                         reinterpret_cast<uint32_t*>(dig_base), ws.big_count);
-            else hipLaunchKernelGGL((digits_kernel<FrP, uint16_t>), dim3((m + 255) / 256), dim3(256), 0, st, sc, m, dstride, c, w_first, w_count, bias,
-                                    reinterpret_cast<uint16_t*>(dig_base), ws.big_count);
+            int rc = front.digits(sc, m_api, w_first, w_count, st);  // 1. the windows of this run
+            if (rc) return rc;
             ws.w_first = w_first;
             ws.w_count = w_count;
             ws.groups = pre ? 1u : (uint32_t)w_count;
-            int rc = run_stages(m, dstride, st, nullptr, phase);
-            if (rc) return rc;
+            if ((rc = run_stages(m, dstride, st, nullptr, phase))) return rc;
             if (phase == 0) ZK_HIP(hipEventRecord(ev_end, st));
         }
         if (phase == 1) q_sorted = true;
@@ -762,9 +564,9 @@ struct MsmPlan : MsmPlanBase {
     int export_sort(SortExport* out) override {
         std::lock_guard<std::mutex> lock(mu);
         if ((!q_pending && !q_sorted) || q_m == 0) return fail(ZK_ERR_ARG, "the lending plan has no run in flight");
-        out->sorted = ws.sorted; out->bstart = ws.bstart; out->sstart = ws.sstart;
-        out->big_list = ws.big_list; out->big_count = ws.big_count;
-        out->n = n; out->m = q_m; out->seg_len = ws.seg_len; out->groups = ws.groups;
+        out->view = front.view();
+        out->view.seg_len = ws.seg_len;
+        out->n = n; out->m = q_m; out->groups = ws.groups;
         out->c = c; out->nwin = nwin; out->w_first = q_first; out->w_count = q_count;
         out->pw_first = pw_first; out->pw_count = pw_count; out->scalar_bits = FrP::BITS; out->pre = pre; out->glv = glv;
         out->endo = glv ? G::ENDO_ID : 0;

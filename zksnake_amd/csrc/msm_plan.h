@@ -1,5 +1,6 @@
 // msm_plan.h -- interface between the C API (msm.hip) and the per-group kernel translation units
-// (msm_group.hip compiled once per curve group, so the four instantiations build in parallel).
+// (msm_group.hip compiled once per curve group, so the four instantiations build in parallel); the group-independent
+// front of a plan, digits and sort, is MsmFront (msm_front.h), compiled once.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -7,6 +8,7 @@
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include "../../include/zkmi.h"
+#include "msm_front.h"
 
 namespace zkmi {
 
@@ -20,9 +22,9 @@ struct DeviceBlock {
 // what a plan with a run in flight lends to a second plan that multiplies the SAME scalars against other bases of the
 // same length (Groth16: <tau_1, v> in G1 and <tau_2, v> in G2): the digits and the sorted entry list
 struct SortExport {
-    const uint32_t *sorted = nullptr, *bstart = nullptr, *sstart = nullptr, *big_list = nullptr, *big_count = nullptr;
+    SortedView view;
     uint64_t n = 0;
-    uint32_t m = 0, seg_len = 0, groups = 0;
+    uint32_t m = 0, groups = 0;
     int c = 0, nwin = 0, w_first = 0, w_count = 0, pw_first = 0, pw_count = 0, scalar_bits = 0;
     bool pre = false, glv = false;
     int endo = 0;                       // which endomorphism split the scalars (curve * 2 + group; 0 = none): digits of different splits do not mix

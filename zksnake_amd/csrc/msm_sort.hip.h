@@ -1,6 +1,7 @@
 // msm_sort.hip.h -- stages 1-4 of the MSM pipeline: scalar digits (plain and split by the endomorphism), the one-level,
-// bucket-range and two-level counting sorts, and the scans between them.  Group-independent: compiled into part 0 of every
-// group translation unit only (msm_group.hip).  Pipeline overview: msm_impl.hip.h.
+// bucket-range and two-level counting sorts, and the scans between them.  Group-independent, and included by msm_front.hip
+// ALONE: the kernels are static, so a second includer would launch copies that the attributes set there do not cover.
+// Pipeline overview: msm_impl.hip.h.
 #pragma once
 #include "msm_common.hip.h"
 
