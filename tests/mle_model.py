@@ -1,7 +1,8 @@
 """Integer model of multilinear polynomials and the sumcheck protocol, written from the definitions with Python integers
 only.  A polynomial in n variables is the list of its 2^n values over {0,1}^n; variable 0 is the least significant bit of
 the list index.  The GPU kernels (csrc/mle.hip) and the Python front end (mle.py, subprotocol/sumcheck.py) are compared
-with it by ==."""
+with it by ==.  The last two sections give exact expectations for tables too large for lists: closed forms on geometric
+tables, and one table whose coefficients are known outright."""
 
 import hashlib
 
@@ -208,3 +209,127 @@ def verify(n, claim, rounds, degree_bound, p, transcript=None, final=None):
     if final is not None and final(rs) != poly_at(rounds[-1], r, p):
         return False
     return rs
+
+
+# ---- geometric tables: closed forms where the lists above cannot follow ----
+# A table T[i] = c g^i is the triple (c, g, log_n).  Every operation above maps a geometric table to a geometric table or to a
+# geometric series, so the expectations below cost O(log n) integer operations at any size.  tests/test_mle_model.py holds
+# each of them to the definitions above at small sizes, including the ratios at which a series degenerates.
+def geo_table(tab, p):
+    c, g, log_n = tab
+    return [c * pow(g, i, p) % p for i in range(1 << log_n)]
+
+
+def geo_sum(first, ratio, count, p):
+    """first (1 + ratio + .. + ratio^(count-1))"""
+    ratio %= p
+    if ratio == 1:
+        return first * count % p
+    return first * (pow(ratio, count, p) - 1) * pow(ratio - 1, -1, p) % p
+
+
+def geo_fix(tab, rs, p):
+    """T[2j] + r (T[2j+1] - T[2j]) = c (1 + r (g - 1)) (g^2)^j"""
+    c, g, log_n = tab
+    assert len(rs) <= log_n
+    for r in rs:
+        c, g, log_n = c * (1 + r * (g - 1)) % p, g * g % p, log_n - 1
+    return c, g, log_n
+
+
+def geo_evaluate(tab, point, p):
+    assert len(point) == tab[2]
+    return geo_fix(tab, point, p)[0]
+
+
+def geo_total(tab, p):
+    c, g, log_n = tab
+    return geo_sum(c, g, 1 << log_n, p)
+
+
+def geo_round_sums(tabs, terms, p):
+    """round_sums: pair j of a table is c g^(2j) (1, g), so its line at X is c (1 + X (g - 1)) (g^2)^j and a term is one series"""
+    log_n = tabs[0][2]
+    s = [0, 0, 0, 0]
+    for coef, which in terms:
+        for x in range(4):
+            first, ratio = coef, 1
+            for i in which:
+                c, g, _ = tabs[i]
+                first = first * c % p
+                if log_n:
+                    first = first * (1 + x * (g - 1)) % p
+                    ratio = ratio * g * g % p
+            s[x] = (s[x] + (geo_sum(first, ratio, 1 << (log_n - 1), p) if log_n else first)) % p
+    return s
+
+
+def geo_coefficient(tab, i, p):
+    """f = c prod_b (1 + x_b (g^(2^b) - 1))"""
+    c, g, log_n = tab
+    assert 0 <= i < 1 << log_n
+    b = 0
+    while i >> b:
+        if (i >> b) & 1:
+            c = c * (pow(g, 1 << b, p) - 1) % p
+        b += 1
+    return c % p
+
+
+def geo_permuted_at(tab, perm, j, p):
+    """element j of permute(table, perm): bit t of j is bit perm[t] of the source index"""
+    c, g, _ = tab
+    return c * pow(g, sum(((j >> t) & 1) << src for t, src in enumerate(perm)), p) % p
+
+
+def geo_f_value(tabs, terms, point, p):
+    vals = [geo_evaluate(t, point, p) for t in tabs]
+    acc = 0
+    for c, which in terms:
+        for i in which:
+            c = c * vals[i] % p
+        acc += c
+    return acc % p
+
+
+def geo_prove(tabs, terms, p, transcript=None):
+    """prove(), line for line, on triples"""
+    n = tabs[0][2]
+    s = geo_round_sums(tabs, terms, p)
+    claim = (s[0] + s[1]) % p if n else s[0]
+    tr = transcript or Transcript(b"sumcheck", p)
+    tr.append(claim)
+    rounds, rs = [], []
+    for rnd in range(n):
+        if rnd:
+            r = tr.challenge()
+            rs.append(r)
+            tabs = [geo_fix(t, [r], p) for t in tabs]
+            s = geo_round_sums(tabs, terms, p)
+        coeffs = interpolate(s, p)
+        tr.append(coeffs)
+        rounds.append(coeffs)
+    rs.append(tr.challenge())
+    return claim, rounds, rs
+
+
+# ---- the table T[i] = p - 1 - i, which needs no model ----
+def descending_limbs(p, log_n):
+    """T[i] = p - 1 - i as a (2^log_n, 4) uint64 limb array: only the low limb changes while 2^log_n stays below it"""
+    import numpy as np
+    low = (p - 1) & ((1 << 64) - 1)
+    assert (1 << log_n) <= low
+    out = np.empty((1 << log_n, 4), dtype=np.uint64)
+    out[:, 0] = np.uint64(low) - np.arange(1 << log_n, dtype=np.uint64)
+    for k in (1, 2, 3):
+        out[:, k] = np.uint64(((p - 1) >> (64 * k)) & ((1 << 64) - 1))
+    return out
+
+
+def descending_coefficient_limbs(p, log_n):
+    """its coefficients: f = (p - 1) - sum_b 2^b x_b, so p - 1 at index 0, p - 2^b at index 2^b and zero elsewhere"""
+    import numpy as np
+    out = np.zeros((1 << log_n, 4), dtype=np.uint64)
+    for i, v in [(0, p - 1)] + [(1 << b, p - (1 << b)) for b in range(log_n)]:
+        out[i] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint64)
+    return out

@@ -186,3 +186,133 @@ def test_sumcheck_verify_is_host_only_on_a_model_proof(name, p):
     # the host interpolation of the prover gives the model's coefficients
     s = M.round_sums(tables, GKR_TERMS, p)
     assert round_polynomial(s, p).coeffs() == M.interpolate(s, p)
+
+
+# ---- the closed forms on geometric tables (the reference of tests/test_gpu_fr_large.py) against the definitions ----
+
+GEO_SIZES = (0, 1, 2, 5, 9)
+GEO_TERMS = {
+    "degree 1": [(1, (0,))],
+    "degree 2": [(1, (0, 1))],
+    "degree 3": [(5, (0, 1, 2))],
+    "one table twice": [(-1, (0, 0))],
+    "mixed": [(-1, (3, 3, 1)), (3, (2,)), (1, (0, 1)), (0, (1, 2))],
+    "gkr": GKR_TERMS,
+}
+
+
+def _root_of_unity_16(p):
+    for x in range(2, 50):
+        w = pow(x, (p - 1) // 16, p)
+        if pow(w, 8, p) != 1:
+            return w
+    raise AssertionError("no element of order 16 found")
+
+
+def _geo_ratios(rnd, p):
+    """random full-width ratios and the ones at which a series degenerates: g = 1 (a constant table), g = p - 1 (g^2 = 1, and
+    1 + X (g - 1) = 0 at X = 1/2), w of order 16 (g^2 becomes 1 after three folds) with w^7 beside it (the product of the two
+    squared ratios is 1 at once)"""
+    w = _root_of_unity_16(p)
+    return {
+        "random": [rnd.randrange(2, p) for _ in range(4)],
+        "g = 1": [1, rnd.randrange(2, p), 1, 1],
+        "g = p - 1": [p - 1, p - 1, rnd.randrange(2, p), p - 1],
+        "order 16": [w, pow(w, 7, p), pow(w, 3, p), pow(w, 5, p)],
+    }
+
+
+def _geo_tables(rnd, p, log_n, ratios):
+    return [(rnd.randrange(1, p), g, log_n) for g in ratios]
+
+
+def _terms(terms, p):
+    return [(c % p, which) for c, which in terms]
+
+
+@pytest.mark.parametrize("name,p", FIELDS, ids=[f[0] for f in FIELDS])
+def test_geo_sum_is_the_sum(name, p):
+    rnd = random.Random(20)
+    for ratio in (0, 1, p + 1, p - 1, 2, rnd.randrange(p), _root_of_unity_16(p)):
+        first = rnd.randrange(p)
+        for count in (1, 2, 5, 16, 33):
+            assert M.geo_sum(first, ratio, count, p) == sum(first * pow(ratio, i, p) for i in range(count)) % p
+
+
+@pytest.mark.parametrize("log_n", GEO_SIZES)
+@pytest.mark.parametrize("name,p", FIELDS, ids=[f[0] for f in FIELDS])
+def test_geo_fix_total_coefficients_permute_equal_the_definitions(name, p, log_n):
+    rnd = random.Random(21 + log_n)
+    for label, ratios in _geo_ratios(rnd, p).items():
+        for tab in _geo_tables(rnd, p, log_n, ratios):
+            t = M.geo_table(tab, p)
+            assert len(t) == 1 << log_n and t[0] == tab[0]
+            assert M.geo_total(tab, p) == M.total(t, p), label
+            rs = [p - 1, 0, pow(2, -1, p), 1][:log_n] + [rnd.randrange(p) for _ in range(log_n - 4)]
+            for k in range(log_n + 1):
+                assert M.geo_table(M.geo_fix(tab, rs[:k], p), p) == M.fix(t, rs[:k], p), (label, k)
+            assert M.geo_evaluate(tab, rs, p) == M.evaluate(t, rs, p), label
+            assert [M.geo_coefficient(tab, i, p) for i in range(1 << log_n)] == M.coefficients(t, p), label
+            perm = list(range(log_n))
+            rnd.shuffle(perm)
+            for pm in (perm, perm[::-1], M.swap_perm(log_n, 0, log_n - 2, 2) if log_n >= 4 else perm):
+                assert [M.geo_permuted_at(tab, pm, j, p) for j in range(1 << log_n)] == M.permute(t, pm), (label, pm)
+
+
+@pytest.mark.parametrize("log_n", GEO_SIZES)
+@pytest.mark.parametrize("name,p", FIELDS, ids=[f[0] for f in FIELDS])
+def test_geo_round_sums_equal_the_definition_down_a_chain_of_folds(name, p, log_n):
+    """every term shape at every level of a chain of folds from log_n to 0: the closed-form round sums against round_sums on the
+    folded lists, and the folded triples against the folded lists"""
+    rnd = random.Random(22 + log_n)
+    for label, ratios in _geo_ratios(rnd, p).items():
+        start = tabs = _geo_tables(rnd, p, log_n, ratios)
+        lists = [M.geo_table(t, p) for t in tabs]
+        rs = [p - 1, pow(2, -1, p), 0][:log_n] + [rnd.randrange(p) for _ in range(log_n - 3)]
+        for level in range(log_n, -1, -1):
+            for shape, terms in GEO_TERMS.items():
+                terms = _terms(terms, p)
+                assert M.geo_round_sums(tabs, terms, p) == M.round_sums(lists, terms, p), (label, shape, level)
+            if level:
+                r = rs[log_n - level]
+                tabs = [M.geo_fix(t, [r], p) for t in tabs]
+                lists = [M.fix(t, [r], p) for t in lists]
+                assert [M.geo_table(t, p) for t in tabs] == lists, (label, level)
+        assert M.geo_f_value(start, GKR_TERMS, rs, p) == M.f_value([M.geo_table(t, p) for t in start], GKR_TERMS, rs, p), label
+
+
+@pytest.mark.parametrize("shape", ["degree 1", "degree 2", "gkr"])
+@pytest.mark.parametrize("name,p", FIELDS, ids=[f[0] for f in FIELDS])
+def test_geo_prove_is_prove(name, p, shape):
+    from test_gpu_sumcheck import shapes
+    terms = shapes(p)[shape]
+    rnd = random.Random(23)
+    for log_n in (0, 1, 2, 5, 9):
+        for label, ratios in _geo_ratios(rnd, p).items():
+            tabs = _geo_tables(rnd, p, log_n, ratios)
+            try:
+                want = M.prove([M.geo_table(t, p) for t in tabs], terms, p)
+            except TypeError:   # one table whose ratio has a small even order: a round polynomial is zero, which no transcript takes
+                assert shape == "degree 1" and label in ("g = p - 1", "order 16")
+                with pytest.raises(TypeError):
+                    M.geo_prove(tabs, terms, p)
+                continue
+            assert M.geo_prove(tabs, terms, p) == want, (label, log_n)
+    tabs = _geo_tables(rnd, p, 5, _geo_ratios(rnd, p)["random"])
+    a, b = M.Transcript(b"outer", p), M.Transcript(b"outer", p)
+    for tr in (a, b):
+        tr.append(99)
+    assert M.geo_prove(tabs, terms, p, a) == M.prove([M.geo_table(t, p) for t in tabs], terms, p, b) != M.geo_prove(tabs, terms, p)
+
+
+@pytest.mark.parametrize("name,p", FIELDS, ids=[f[0] for f in FIELDS])
+def test_descending_table_and_its_coefficients(name, p):
+    """T[i] = p - 1 - i, built in limbs: the table and its coefficient table (p - 1 at 0, p - 2^b at 2^b, zero elsewhere)"""
+    for log_n in (0, 1, 6):
+        n = 1 << log_n
+        t = N.limbs_to_ints(M.descending_limbs(p, log_n))
+        assert t == [p - 1 - i for i in range(n)]
+        want = N.limbs_to_ints(M.descending_coefficient_limbs(p, log_n))
+        assert want == M.coefficients(t, p)
+        assert [i for i, v in enumerate(want) if v] == sorted({0} | {1 << b for b in range(log_n)})
+    assert ((p - 1) & ((1 << 64) - 1)) > 1 << 25   # the low limb never borrows at the sizes the GPU tests use

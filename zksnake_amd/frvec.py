@@ -40,10 +40,15 @@ class DevVec:
         self.n = n
         nbytes = 32 * max(n, 1)
         bufs = _POOL.get(nbytes)
-        if bufs:
-            self.buf = bufs.pop()
+        self.buf = None
+        while bufs and self.buf is None:
+            buf = bufs.pop()
             _POOL_BYTES[0] -= nbytes
-        else:
+            # A vector that dies in a reference cycle (the frames of a caught exception, say) is finalised together with its
+            # buffer, in either order: the buffer may have come here first and been freed afterwards.
+            if buf.ptr is not None:
+                self.buf = buf
+        if self.buf is None:
             self.buf = DeviceBuffer(nbytes)
         if zero:
             self.buf.zero()
