@@ -231,6 +231,20 @@ def test_relaxed_g2_step_host_build_and_integer_models(tmp_path):
         assert res.returncode == 0 and "ok" in res.stdout, res.stdout + res.stderr
 
 
+def test_dev_buf_gives_every_block_back_exactly_once(tmp_path):
+    """DevBuf (csrc/dev_buf.h), the owner of every cached device block, against counting stand-ins for the allocator
+    (tests/native/dev_buf_check.cpp): scope end, alloc on a holder, a failing alloc, moves, a double reset, shared ownership
+    and an early return past three buffers each end with the blocks handed out equal to the blocks returned, none of them
+    twice.  A host program under the address and undefined-behaviour sanitizers; no GPU and no device code.  The sanitizer
+    runtimes are linked into the program, so it runs as it is whatever else the environment loads into a process."""
+    import subprocess
+    exe = str(tmp_path / "dev_buf_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                           "-static-libubsan", "-o", exe, os.path.join(ROOT, "tests", "native", "dev_buf_check.cpp")])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0 and res.stdout.count(": ok") == 7 and "all ok" in res.stdout, res.stdout + res.stderr
+
+
 def test_build_script_falls_back_to_plain_hipcc_when_the_pass_pipeline_cannot_be_reproduced(tmp_path):
     """csrc/hipcc_noreassoc.sh drives clang / opt / llc by hand to leave LLVM's `reassociate` pass out of the device pipeline; on a
     toolchain whose O3 pipeline text has no such pass it must not fail the build (round-3 advisor finding) but compile the unit

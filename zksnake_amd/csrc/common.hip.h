@@ -6,6 +6,7 @@
 #include <string>
 #include "../../include/zkmi.h"
 #include "curve.hip.h"
+#include "dev_buf.h"
 #include "host64.hip.h"
 
 #if defined(__HIPCC__)
@@ -40,15 +41,12 @@ inline int fail(int code, const std::string& msg) {
 // hipMalloc / hipFree cost 50-200 us each and synchronise the device; a one-shot `zk_msm` (plan create + run + destroy)
 // makes ~25 of them, 3.5 ms for a two-point MSM.  Freed blocks are kept by exact size (plans of the same shape ask for
 // the same sizes again) up to a byte budget; blocks above the budget go straight back to HIP.  zk_shutdown() empties it.
-int dev_alloc_cached(void** p, size_t bytes);
-void dev_free_cached(void* p);
 void dev_cache_release();
 // streams and pinned host blocks are pooled the same way (hipStreamCreate costs ~1.5 ms, hipHostMalloc ~0.5 ms)
 int stream_acquire(bool high_priority, hipStream_t* out);
 void stream_release(bool high_priority, hipStream_t st);
 int pinned_alloc_cached(void** p, size_t bytes);
 void pinned_free_cached(void* p);
-#define ZK_ALLOC(ptr, bytes) ZK_HIP_RC(::zkmi::dev_alloc_cached((void**)(ptr), (bytes)))
 #define ZK_HIP_RC(expr)                    \
     do {                                   \
         int _rc = (expr);                  \

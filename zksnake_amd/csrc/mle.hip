@@ -18,6 +18,7 @@
 #include "fr_mem.hip.h"
 
 namespace zkmi {
+using mem::DevBuf;
 
 constexpr int MLE_TILE_LOG = ZK_MLE_TILE_LOG;
 constexpr int MLE_TILE = 1 << MLE_TILE_LOG;   // elements per tile == threads per workgroup
@@ -254,14 +255,11 @@ static int mle_fix_impl(int log_n, const void* in, int k, const uint64_t* r, voi
     const uint64_t eb = P::W * 4;
     if (ranges_overlap(in, eb << log_n, out, eb << (log_n - k))) return fail(ZK_ERR_ARG, "mle_fix: d_out overlaps d_in");
     const uint64_t need = fix_work_elems(log_n, k);
-    uint32_t* work = nullptr;
-    if (need) ZK_ALLOC(&work, need * eb);
-    int rc = fix_chain<P>(log_n, (const uint32_t*)in, k, r, (uint32_t*)out, work, st);
-    if (work) {  // the intermediate tables go back to the allocator only after the chain has run
-        if (rc == ZK_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(ZK_ERR_HIP, "mle_fix: kernel failed");
-        dev_free_cached(work);
-    }
-    return rc;
+    DevBuf work;
+    if (need) ZK_HIP_RC(work.alloc(need * eb));
+    ZK_HIP_RC(fix_chain<P>(log_n, (const uint32_t*)in, k, r, (uint32_t*)out, work.as(), st));
+    if (work) ZK_HIP(hipStreamSynchronize(st));  // the intermediate tables go back to the allocator only after the chain has run
+    return ZK_OK;
 }
 
 template <class P>
@@ -271,14 +269,14 @@ static int mle_eval_impl(int log_n, const void* x, const uint64_t* point, uint64
     const uint64_t eb = P::W * 4;
     const uint64_t need = fix_work_elems(log_n, log_n) + 1;   // the chain's intermediates, then the one-element result
     if (d_work && ranges_overlap(x, eb << log_n, d_work, need * eb)) return fail(ZK_ERR_ARG, "mle_eval: d_work overlaps d_x");
-    uint32_t* work = (uint32_t*)d_work;
-    if (!work) ZK_ALLOC(&work, need * eb);
+    DevBuf own;  // the work memory, when the caller passed none
+    if (!d_work) ZK_HIP_RC(own.alloc(need * eb));
+    uint32_t* work = d_work ? (uint32_t*)d_work : own.as();
     uint32_t* res = work + (need - 1) * P::W;
-    int rc = fix_chain<P>(log_n, (const uint32_t*)x, log_n, point, res, need > 1 ? work : nullptr, st);
-    if (rc == ZK_OK && (hipMemcpyAsync(out, res, eb, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-        rc = fail(ZK_ERR_HIP, "mle_eval: kernel or copy back failed");
-    if (!d_work) dev_free_cached(work);
-    return rc;
+    ZK_HIP_RC(fix_chain<P>(log_n, (const uint32_t*)x, log_n, point, res, need > 1 ? work : nullptr, st));
+    ZK_HIP(hipMemcpyAsync(out, res, eb, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
 }
 
 template <class P>
@@ -289,17 +287,15 @@ static int mle_sum_impl(uint64_t n, const void* x, uint64_t* out, hipStream_t st
     if (n == 0) return ZK_OK;
     const size_t eb = P::W * 4;
     const unsigned blocks = (unsigned)std::min<uint64_t>((n + MLE_TILE - 1) / MLE_TILE, MLE_MAX_PARTIALS);
-    uint32_t* part = nullptr;   // blocks partial sums | the result
-    ZK_ALLOC(&part, (size_t)(blocks + 1) * eb);
-    uint32_t* res = part + (size_t)blocks * P::W;
-    int rc = ZK_OK;
+    DevBuf part_buf;   // blocks partial sums | the result
+    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * eb));
+    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * P::W;
     hipLaunchKernelGGL(mle_sum_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, n, (const uint32_t*)x, part);
     hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 1, part, res);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, res, eb, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        rc = fail(ZK_ERR_HIP, "mle_sum: kernel or copy back failed");
-    dev_free_cached(part);
-    return rc;
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(out, res, eb, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
 }
 
 template <class P>
@@ -397,17 +393,15 @@ static int sumcheck_round_impl(int log_n, int n_tables, const void* const* table
     const int single = vars == 0;
     const uint64_t pairs = single ? 1 : 1ull << (vars - 1);
     const unsigned blocks = (unsigned)std::min<uint64_t>((pairs + MLE_TILE - 1) / MLE_TILE, MLE_MAX_PARTIALS);
-    uint32_t* part = nullptr;   // blocks x 4 partial sums | the 4 results
-    ZK_ALLOC(&part, (size_t)(blocks + 1) * 4 * eb);
-    uint32_t* res = part + (size_t)blocks * 4 * P::W;
-    int rc = ZK_OK;
+    DevBuf part_buf;   // blocks x 4 partial sums | the 4 results
+    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * 4 * eb));
+    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * 4 * P::W;
     hipLaunchKernelGGL(sumcheck_round_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, pairs, single, a, part);
     hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 4, part, res);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(s_out, res, 4 * eb, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        rc = fail(ZK_ERR_HIP, "sumcheck_round: kernel or copy back failed");
-    dev_free_cached(part);
-    return rc;
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(s_out, res, 4 * eb, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
 }
 
 }  // namespace zkmi

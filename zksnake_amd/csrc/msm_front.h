@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 #include "../../include/zkmi.h"
+#include "dev_buf.h"
 
 namespace zkmi {
 
@@ -34,7 +35,7 @@ public:
     MsmFront() = default;
     MsmFront(const MsmFront&) = delete;
     MsmFront& operator=(const MsmFront&) = delete;
-    ~MsmFront();  // blocks go back to the caching allocator: the owner makes sure that nothing of it is in flight
+    ~MsmFront() = default;  // blocks go back to the caching allocator: the owner makes sure that nothing of it is in flight
 
     // Plan creation, in the order MsmPlan::init calls them (its own allocations sit in between).  `opt` is the owning plan's:
     // two_level_sort is read at every sort, fine_log and sort_workgroups here.
@@ -46,14 +47,14 @@ public:
     int digits(const uint32_t* scalars, uint32_t m_api, int w_first, int w_count, hipStream_t st);
     // stages 2-4 over the m entries per window that digits() left: histogram, scans, scatter -> view()
     int sort(uint32_t m, uint32_t dstride, uint32_t seg_len, int w_first, int w_count, uint32_t groups, hipStream_t st);
-    SortedView view() const { return {sorted, bstart, sstart, big_list, big_count, seg_len}; }
+    SortedView view() const { return {sorted.as(), bstart.as(), sstart.as(), big_list.as(), big_count.as(), seg_len}; }
 
     bool two_level_ok() const;
-    bool has_two_level_buffers() const { return tmp_ref != nullptr; }
-    uint32_t* scalars_buf() const { return d_scalars; }  // staging for scalars that arrive from the host
+    bool has_two_level_buffers() const { return (bool)tmp_ref; }
+    uint32_t* scalars_buf() const { return d_scalars.as(); }  // staging for scalars that arrive from the host
 
     // zk_msm_plan_debug_view: the digits and what the last sort of this front did (sort() stores it; nothing reads it on the run path)
-    const void* digits_buf() const { return d_dig; }
+    const void* digits_buf() const { return d_dig.as<void>(); }
     int view_route = ZK_MSM_ROUTE_NONE, view_fine_log = 0;
     uint32_t view_dstride = 0;
     bool view_split_fine() const { return view_route >= ZK_MSM_ROUTE_TWO_LEVEL_DERIVE && tmp_fine; }
@@ -67,16 +68,16 @@ private:
     template <class FrP>
     void launch_digits(const uint32_t* scalars, uint32_t m_api, int w_first, int w_count, hipStream_t st);
 
+    using DevBuf = mem::DevBuf;
     const MsmOptions* opt = nullptr;
     int range_log = 0;      // general mode: log2(buckets per sort workgroup)
     uint32_t bias[13] = {};  // sum_w 2^(c-1) 2^(cw): added to a scalar before it is cut into plain c-bit fields
     uint32_t seg_len = 0;   // of the last sort
-    uint32_t* d_scalars = nullptr;
-    void* d_dig = nullptr;  // windows x (n + 8) digits, uint16_t (c <= 16) or uint32_t
-    uint32_t *hist = nullptr, *total = nullptr, *bstart = nullptr, *sstart = nullptr;
-    uint32_t *bsums = nullptr, *grand = nullptr, *big_list = nullptr, *big_count = nullptr, *sorted = nullptr;
-    uint32_t *tmp_ref = nullptr, *bin_start = nullptr, *slice_sums = nullptr, *bin_tot = nullptr, *bin_runs = nullptr;  // two-level sort
-    uint8_t* tmp_fine = nullptr;  // fine bucket bits of the level-A entries when the reference needs all 31 bits
+    DevBuf d_scalars;
+    DevBuf d_dig;  // windows x (n + 8) digits, uint16_t (c <= 16) or uint32_t
+    DevBuf hist, total, bstart, sstart, bsums, grand, big_list, big_count, sorted;
+    DevBuf tmp_ref, bin_start, slice_sums, bin_tot, bin_runs;  // two-level sort
+    DevBuf tmp_fine;  // bytes: fine bucket bits of the level-A entries when the reference needs all 31 bits
 };
 
 }  // namespace zkmi

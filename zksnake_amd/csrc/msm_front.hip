@@ -7,12 +7,6 @@
 
 namespace zkmi {
 
-MsmFront::~MsmFront() {
-    void* bufs[] = {hist, total, bstart, sstart, bsums, grand, big_list, big_count, sorted, tmp_ref, tmp_fine, bin_start, slice_sums, bin_tot, bin_runs,
-                    d_scalars, d_dig};
-    for (void* q : bufs) dev_free_cached(q);
-}
-
 int MsmFront::init(const FrontLayout& layout, const MsmOptions* options) {
     static_cast<FrontLayout&>(*this) = layout;
     opt = options;
@@ -34,8 +28,8 @@ int MsmFront::init(const FrontLayout& layout, const MsmOptions* options) {
 #define ZK_FRONT_WORDS(FR) scalar_words = FR::W
     ZK_DISPATCH_FR(curve, ZK_FRONT_WORDS);
 #undef ZK_FRONT_WORDS
-    ZK_ALLOC(&d_scalars, n_api * scalar_words * 4);
-    ZK_ALLOC(&d_dig, (size_t)pw_count * (n + 8) * (wide ? 4 : 2));
+    ZK_HIP_RC(d_scalars.alloc(n_api * scalar_words * 4));
+    ZK_HIP_RC(d_dig.alloc((size_t)pw_count * (n + 8) * (wide ? 4 : 2)));
     if (wide && !two_level_ok()) return fail(ZK_ERR_ARG, "this size does not fit the two-level sort that wide windows need");
     return ZK_OK;
 }
@@ -44,22 +38,22 @@ int MsmFront::alloc_workspace() {
     const uint64_t max_sets = pre ? 1ull : (uint64_t)pw_count;
     const uint64_t keys = max_sets * B, entries = (uint64_t)pw_count * n;
     // windows x chunks <= max(256, windows) sub-histograms: of all B buckets (one-level sort) or of the coarse bins only
-    ZK_ALLOC(&hist, (size_t)std::max<uint64_t>(256, pw_count) * (wide ? (B >> fine_log_for(n)) : B) * 4);
-    ZK_ALLOC(&total, keys * 4);
-    ZK_ALLOC(&bstart, (keys + 1) * 4);
-    ZK_ALLOC(&sstart, (keys + 1) * 4);
-    ZK_ALLOC(&bsums, ((keys + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4);
-    ZK_ALLOC(&grand, 4);
-    ZK_ALLOC(&big_list, keys * 4);
-    ZK_ALLOC(&big_count, 8);
-    ZK_ALLOC(&sorted, entries * 4);
+    ZK_HIP_RC(hist.alloc((size_t)std::max<uint64_t>(256, pw_count) * (wide ? (B >> fine_log_for(n)) : B) * 4));
+    ZK_HIP_RC(total.alloc(keys * 4));
+    ZK_HIP_RC(bstart.alloc((keys + 1) * 4));
+    ZK_HIP_RC(sstart.alloc((keys + 1) * 4));
+    ZK_HIP_RC(bsums.alloc(((keys + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4));
+    ZK_HIP_RC(grand.alloc(4));
+    ZK_HIP_RC(big_list.alloc(keys * 4));
+    ZK_HIP_RC(big_count.alloc(8));
+    ZK_HIP_RC(sorted.alloc(entries * 4));
     if (two_level_ok()) {
-        ZK_ALLOC(&tmp_ref, entries * 4);
-        if (split_fine()) ZK_ALLOC(&tmp_fine, entries);
-        ZK_ALLOC(&bin_start, (max_sets * (B >> fine_log_for(n)) + 1) * 4);
-        ZK_ALLOC(&slice_sums, 4096 * BINS_SLICES * 4);
-        ZK_ALLOC(&bin_tot, 4096 * 4);
-        ZK_ALLOC(&bin_runs, max_sets * (B >> fine_log_for(n)) * 4);
+        ZK_HIP_RC(tmp_ref.alloc(entries * 4));
+        if (split_fine()) ZK_HIP_RC(tmp_fine.alloc(entries));
+        ZK_HIP_RC(bin_start.alloc((max_sets * (B >> fine_log_for(n)) + 1) * 4));
+        ZK_HIP_RC(slice_sums.alloc(4096 * BINS_SLICES * 4));
+        ZK_HIP_RC(bin_tot.alloc(4096 * 4));
+        ZK_HIP_RC(bin_runs.alloc(max_sets * (B >> fine_log_for(n)) * 4));
     }
     return ZK_OK;
 }
@@ -89,9 +83,9 @@ int MsmFront::chunks_for(int windows, uint64_t count) {
 
 int MsmFront::exclusive_scan(const uint32_t* in, uint32_t cnt, uint32_t* out, hipStream_t st) {
     uint32_t blocks = (cnt + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    hipLaunchKernelGGL(scan_block_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, in, cnt, out, bsums);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, bsums, blocks, grand);
-    hipLaunchKernelGGL(scan_add_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, out, cnt, bsums, grand);
+    hipLaunchKernelGGL(scan_block_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, in, cnt, out, bsums.as());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, st, bsums.as(), blocks, grand.as());
+    hipLaunchKernelGGL(scan_add_kernel, dim3(blocks), dim3(SCAN_BLOCK), 0, st, out, cnt, bsums.as(), grand.as());
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
@@ -133,7 +127,7 @@ bool MsmFront::two_level_ok() const {
 
 // digit rows are stored relative to the plan's first window; the kernels index them with absolute windows
 uintptr_t MsmFront::dig_base(uint32_t dstride) const {
-    return reinterpret_cast<uintptr_t>(d_dig) - (uintptr_t)pw_first * dstride * (wide ? 4 : 2);
+    return reinterpret_cast<uintptr_t>(d_dig.as<void>()) - (uintptr_t)pw_first * dstride * (wide ? 4 : 2);
 }
 
 // 1. digits (the windows of this run)
@@ -143,6 +137,7 @@ void MsmFront::launch_digits(const uint32_t* sc, uint32_t m_api, int w_first, in
     const uint32_t dstride = (m + 7u) & ~7u;
     DigitBias b;
     memcpy(b.v, bias, sizeof(b.v));
+    uint32_t* const big_count = this->big_count.as();
     if (glv) hipLaunchKernelGGL(glv_digits_kernel<FrP>, dim3((m_api + 255) / 256), dim3(256), 0, st, sc, m_api, dstride, c, w_first, w_count, b,
                                 *glv, reinterpret_cast<uint16_t*>(dig_base(dstride)), big_count);
     else if (wide) hipLaunchKernelGGL((digits_kernel<FrP, uint32_t>), dim3((m + 255) / 256), dim3(256), 0, st, sc, m, dstride, c, w_first, w_count, b,
@@ -167,7 +162,13 @@ int MsmFront::sort(uint32_t m, uint32_t dstride, uint32_t run_seg_len, int w_fir
     const uint32_t* d_dig32 = reinterpret_cast<const uint32_t*>(dig_base(dstride));
     // general mode, small inputs: bucket-range partition (measured faster up to 2^18); otherwise the two-level sort
     const bool ranged = !pre && !wide && m < (1u << 19);
-    const bool two_level = !ranged && tmp_ref != nullptr && opt->two_level_sort;
+    const bool two_level = !ranged && this->tmp_ref && opt->two_level_sort;
+    // the kernels take plain pointers: the members' blocks under the members' names
+    uint32_t *const hist = this->hist.as(), *const total = this->total.as(), *const bstart = this->bstart.as(), *const sstart = this->sstart.as();
+    uint32_t *const bsums = this->bsums.as(), *const grand = this->grand.as(), *const big_list = this->big_list.as(), *const big_count = this->big_count.as();
+    uint32_t *const sorted = this->sorted.as(), *const tmp_ref = this->tmp_ref.as(), *const bin_start = this->bin_start.as(), *const slice_sums = this->slice_sums.as();
+    uint32_t *const bin_tot = this->bin_tot.as(), *const bin_runs = this->bin_runs.as();
+    uint8_t* const tmp_fine = this->tmp_fine.as<uint8_t>();
     view_route = ranged ? ZK_MSM_ROUTE_RANGED : ZK_MSM_ROUTE_ONE_LEVEL;   // zk_msm_plan_debug_view
     view_fine_log = 0;
     view_dstride = dstride;

@@ -41,6 +41,7 @@
 #include "msm_reduce.hip.h"
 
 namespace zkmi {
+using mem::DevBuf;
 
 #if defined(ZK_GROUP) && (!defined(ZK_PART) || ZK_PART == 0)
 // the plan's translation unit does not instantiate the heavy kernels (see msm_group.hip)
@@ -67,8 +68,9 @@ static int precompute_table(uint32_t* table, uint64_t n, int c, int w_first, int
     typedef typename G::F F;
     constexpr int AW = 2 * F::LIMBS, XW = 4 * F::LIMBS;
     if (w_first == 0 && w_count == 1) return ZK_OK;
-    uint32_t* temp = nullptr;
-    ZK_ALLOC(&temp, n * XW * 4);
+    DevBuf temp_buf;
+    ZK_HIP_RC(temp_buf.alloc(n * XW * 4));
+    uint32_t* const temp = temp_buf.as();
     const unsigned blocks = (unsigned)((n + 255) / 256);
     const unsigned nblocks = (unsigned)((n + (uint64_t)NORM_THREADS * NORM_E - 1) / ((uint64_t)NORM_THREADS * NORM_E));
     hipLaunchKernelGGL(dbl_rows_kernel<G>, dim3(blocks), dim3(256), 0, 0, temp, n, c * w_first, (const uint32_t*)table);
@@ -77,10 +79,8 @@ static int precompute_table(uint32_t* table, uint64_t n, int c, int w_first, int
         hipLaunchKernelGGL(dbl_rows_kernel<G>, dim3(blocks), dim3(256), 0, 0, temp, n, c, (const uint32_t*)nullptr);
         hipLaunchKernelGGL(normalize_kernel<G>, dim3(nblocks), dim3(NORM_THREADS), 0, 0, temp, n, table + (size_t)k * n * AW, 0);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    dev_free_cached(temp);
-    ZK_HIP(e);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipDeviceSynchronize());
     return ZK_OK;
 }
 
@@ -88,17 +88,18 @@ static int precompute_table(uint32_t* table, uint64_t n, int c, int w_first, int
 template <class G>
 struct FixedTable {
     std::vector<uint64_t> base;   // canonical affine limbs the table was built for
-    uint32_t* d_table = nullptr;
+    DevBuf d_table;
     int nwin = 0;
     std::mutex mu;
+    // never destroyed: the table goes back through release() (zk_shutdown) only, and nothing runs at process exit, when the
+    // allocator's maps or the HIP runtime may already be gone
     static FixedTable& get() {
-        static FixedTable t;
-        return t;
+        static FixedTable* const t = new FixedTable();
+        return *t;
     }
     void release() {
         std::lock_guard<std::mutex> lock(mu);
-        if (d_table) dev_free_cached(d_table);
-        d_table = nullptr;
+        d_table.reset();
         base.clear();
     }
     // caller holds mu
@@ -108,8 +109,7 @@ struct FixedTable {
         constexpr int AW = 2 * F::LIMBS, XW = 4 * F::LIMBS;
         const size_t words64 = AW / 2;
         if (d_table && base.size() == words64 && memcmp(base.data(), base_limbs, words64 * 8) == 0) return ZK_OK;
-        if (d_table) dev_free_cached(d_table);
-        d_table = nullptr;
+        d_table.reset();
         base.clear();
         nwin = (FrP::BITS + 1 + FIXED_C - 1) / FIXED_C;
         // window bases 2^(16 j) G on the host (16 points)
@@ -126,25 +126,17 @@ struct FixedTable {
             }
         }
         const uint64_t rows = (uint64_t)nwin * FIXED_HALF;
-        uint32_t *d_wb = nullptr, *temp = nullptr;
-        ZK_ALLOC(&d_table, rows * AW * 4);
-        hipError_t e = dev_alloc_cached((void**)&d_wb, wb.size() * 4) == ZK_OK ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = dev_alloc_cached((void**)&temp, rows * XW * 4) == ZK_OK ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipMemcpy(d_wb, wb.data(), wb.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(fixed_table_kernel<G>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, 0, d_wb, nwin, temp);
-            hipLaunchKernelGGL(normalize_kernel<G>, dim3((unsigned)((rows + (uint64_t)NORM_THREADS * NORM_E - 1) / ((uint64_t)NORM_THREADS * NORM_E))),
-                               dim3(NORM_THREADS), 0, 0, temp, rows, d_table, 0);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
-        if (d_wb) dev_free_cached(d_wb);
-        if (temp) dev_free_cached(temp);
-        if (e != hipSuccess) {
-            dev_free_cached(d_table);
-            d_table = nullptr;
-            return fail(ZK_ERR_HIP, std::string("fixed-base table: ") + hipGetErrorString(e));
-        }
+        DevBuf table, d_wb, temp;  // the table becomes the member once it is complete
+        ZK_HIP_RC(table.alloc(rows * AW * 4));
+        ZK_HIP_RC(d_wb.alloc(wb.size() * 4));
+        ZK_HIP_RC(temp.alloc(rows * XW * 4));
+        ZK_HIP(hipMemcpy(d_wb.as(), wb.data(), wb.size() * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(fixed_table_kernel<G>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, 0, d_wb.as(), nwin, temp.as());
+        hipLaunchKernelGGL(normalize_kernel<G>, dim3((unsigned)((rows + (uint64_t)NORM_THREADS * NORM_E - 1) / ((uint64_t)NORM_THREADS * NORM_E))),
+                           dim3(NORM_THREADS), 0, 0, temp.as(), rows, table.as(), 0);
+        ZK_HIP(hipGetLastError());
+        ZK_HIP(hipDeviceSynchronize());
+        d_table = std::move(table);
         base.assign(base_limbs, base_limbs + words64);
         return ZK_OK;
     }
@@ -162,8 +154,8 @@ struct MsmPlan : MsmPlanBase {
 
     // device workspace of one run (stages 5..7; the sort's is the front's)
     struct Work {
-        uint32_t *partials = nullptr, *buckets = nullptr, *rows = nullptr, *fin = nullptr;
-        uint32_t* parts = nullptr;  // partial row / column sums of the two-step strided sums
+        DevBuf partials, buckets, rows, fin;
+        DevBuf parts;  // partial row / column sums of the two-step strided sums
         // A recorded event costs ~3 us of idle GPU between two kernels (tools/event_gap_probe.hip), so a run records only the four
         // that order work or bound a stage: ev_start (plan), ev_acc0 = sorted (also the lender's "sorted_ready"), ev_acc1 =
         // accumulated (the gate of the next plan's accumulate kernel), ev_end (plan); ev_accs only when the accumulate kernel
@@ -187,16 +179,15 @@ struct MsmPlan : MsmPlanBase {
     Work ws;
     MsmFront front;  // stages 1-4: scalars -> digits -> sorted entry list
     // shared device buffers
-    std::shared_ptr<DeviceBlock> bases_block;  // the (table of) bases: shared by the clones of a plan
+    std::shared_ptr<DevBuf> bases_block;  // the (table of) bases: shared by the clones of a plan
     uint32_t* d_bases = nullptr;
     uint32_t* h_final = nullptr;  // pinned: (S, T) per weighted-sum block
     hipEvent_t ev_start = nullptr, ev_end = nullptr;
 
     ~MsmPlan() override {
-        // blocks go back to the caching allocator, which (unlike hipFree) does not wait for the device: make sure no run of
-        // this plan is still in flight
+        // the blocks of ws, front and bases_block go back to the caching allocator after this body, and that (unlike hipFree)
+        // does not wait for the device: make sure no run of this plan is still in flight
         (void)hipDeviceSynchronize();
-        for (void* q : {ws.partials, ws.buckets, ws.rows, ws.parts, ws.fin}) dev_free_cached(q);
         pinned_free_cached(h_final);
         for (hipEvent_t e : {ws.ev_acc0, ws.ev_accs, ws.ev_acc1, ws.ev_release, ev_start, ev_end}) if (e) (void)hipEventDestroy(e);
         stream_release((create_flags & ZK_MSM_HIGH_PRIORITY) != 0, own_stream);
@@ -249,22 +240,18 @@ struct MsmPlan : MsmPlanBase {
             bases_block = share->bases_block;
             d_bases = share->d_bases;
         } else {
-            bases_block = std::make_shared<DeviceBlock>();
-            ZK_ALLOC(&bases_block->ptr, (pre ? (uint64_t)pw_count : 1ull) * n * AW * 4);
-            d_bases = (uint32_t*)bases_block->ptr;
+            bases_block = std::make_shared<DevBuf>();
+            ZK_HIP_RC(bases_block->alloc((pre ? (uint64_t)pw_count : 1ull) * n * AW * 4));
+            d_bases = bases_block->as();
             if (bases_on_device) {
                 hipLaunchKernelGGL(bases_to_mont_kernel<G>, dim3((unsigned)((n_api + 127) / 128)), dim3(128), 0, 0,
                                    (const uint32_t*)bases, n_api, d_bases, glv ? 1 : 0);
             } else {
-                uint32_t* tmp = nullptr;
-                ZK_ALLOC(&tmp, n_api * AW * 4);
-                hipError_t e = hipMemcpy(tmp, bases, n_api * AW * 4, hipMemcpyHostToDevice);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(bases_to_mont_kernel<G>, dim3((unsigned)((n_api + 127) / 128)), dim3(128), 0, 0, tmp, n_api, d_bases, glv ? 1 : 0);
-                    e = hipDeviceSynchronize();
-                }
-                dev_free_cached(tmp);
-                ZK_HIP(e);
+                DevBuf tmp;
+                ZK_HIP_RC(tmp.alloc(n_api * AW * 4));
+                ZK_HIP(hipMemcpy(tmp.as(), bases, n_api * AW * 4, hipMemcpyHostToDevice));
+                hipLaunchKernelGGL(bases_to_mont_kernel<G>, dim3((unsigned)((n_api + 127) / 128)), dim3(128), 0, 0, tmp.as(), n_api, d_bases, glv ? 1 : 0);
+                ZK_HIP(hipDeviceSynchronize());
             }
             ZK_HIP(hipGetLastError());
             if (pre) {
@@ -291,11 +278,11 @@ struct MsmPlan : MsmPlanBase {
             const uint32_t seg_full = pick_seg_len(entries);
             const uint64_t max_segs = std::max<uint64_t>(entries / seg_full, std::min<uint64_t>(entries / 8, seg_lanes_at_init)) + keys + 8;
             ZK_HIP_RC(front.alloc_workspace());
-            ZK_ALLOC(&ws.partials, max_segs * XW * 4);
-            ZK_ALLOC(&ws.buckets, keys * XW * 4);
-            ZK_ALLOC(&ws.rows, max_sets * (R + C) * XW * 4);
-            if (sum_part_len() >= 2) ZK_ALLOC(&ws.parts, max_sets * 2 * (uint64_t)(B / sum_part_len()) * XW * 4);
-            ZK_ALLOC(&ws.fin, max_sets * (bpr + bpc) * 2 * XW * 4);
+            ZK_HIP_RC(ws.partials.alloc(max_segs * XW * 4));
+            ZK_HIP_RC(ws.buckets.alloc(keys * XW * 4));
+            ZK_HIP_RC(ws.rows.alloc(max_sets * (R + C) * XW * 4));
+            if (sum_part_len() >= 2) ZK_HIP_RC(ws.parts.alloc(max_sets * 2 * (uint64_t)(B / sum_part_len()) * XW * 4));
+            ZK_HIP_RC(ws.fin.alloc(max_sets * (bpr + bpc) * 2 * XW * 4));
             for (hipEvent_t* e : {&ws.ev_acc0, &ws.ev_accs, &ws.ev_acc1, &ws.ev_release}) ZK_HIP(hipEventCreate(e));
         }
         mark("workspace + events");
@@ -338,6 +325,7 @@ struct MsmPlan : MsmPlanBase {
     // stage 5: the dominant kernel; stage 6: buckets whose entries span several segments (three tiers, one launch)
     int stage_accumulate(uint32_t m, const SortedView& sv, hipStream_t st, bool prio_steps) {
         Work& l = ws;
+        uint32_t *const partials = l.partials.as(), *const buckets = l.buckets.as();
         const uint32_t seg_len = sv.seg_len;
         const uint32_t n_keys = l.groups * B;
         const uint64_t lanes_needed = ((uint64_t)l.w_count * m + seg_len - 1) / seg_len;
@@ -345,15 +333,15 @@ struct MsmPlan : MsmPlanBase {
         if constexpr (AccumulateSplit<G>::ON) {
             if (opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0) {
                 // Fp2 groups: a lane PAIR per segment, every value split by component (fp2_split.hip.h)
-                hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, l.partials, l.buckets);
+                hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, partials, buckets);
                 launched = true;
             }
         }
-        if (!launched) hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, l.partials, l.buckets);
+        if (!launched) hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, partials, buckets);
         ZK_HIP(hipEventRecord(l.ev_acc1, st));
         const uint32_t small_blocks = (2 * n_keys + COMBINE_THREADS - 1) / COMBINE_THREADS;
         hipLaunchKernelGGL(combine_kernel<G>, dim3(small_blocks + COMBINE_WAVE_BLOCKS + COMBINE_BIG_BLOCKS), dim3(COMBINE_THREADS), 0, st,
-                           l.partials, sv.sstart, n_keys, small_blocks, sv.big_list, sv.big_count, l.buckets);
+                           partials, sv.sstart, n_keys, small_blocks, sv.big_list, sv.big_count, buckets);
         ZK_HIP(hipGetLastError());
         return ZK_OK;
     }
@@ -361,6 +349,7 @@ struct MsmPlan : MsmPlanBase {
     // stage 7: sum_b (b + 1) B_b per bucket set down to (S, T) per block of row / column sums, copied to h_final
     int stage_reduce(hipStream_t st) {
         Work& l = ws;
+        uint32_t *const buckets = l.buckets.as(), *const parts = l.parts.as(), *const row_sums = l.rows.as(), *const fin = l.fin.as();
         const uint32_t groups = l.groups;
         const uint32_t n_keys = groups * B;
         // 7. reduce: rows (sum over lo), cols (sum over hi), weighted sums
@@ -373,28 +362,28 @@ struct MsmPlan : MsmPlanBase {
         // worth it from 2^18 buckets on (8 windows of 2^15, or the 2^19-bucket set of a fixed-base plan): with fewer the sums
         // are a latency chain and the second launch only lengthens it (measured: 2^17 buckets 0.223 vs 0.212 ms)
         const uint32_t K = (one_step || n_keys < (1u << 18)) ? 0u : sum_part_len();
-        if (K >= 2 && l.parts && C % K == 0 && R % K == 0 && C / K >= 2 && R / K >= 2) {
+        if (K >= 2 && parts && C % K == 0 && R % K == 0 && C / K >= 2 && R / K >= 2) {
             const uint32_t pr = C / K, pc = R / K;  // partial sums per row sum / per column sum
             // step 1: partial (row r, part p) = sum of buckets r C + p K + [0, K); (column j, part p) = sum of (p K + i) C + j
             SumJob prow = {n_rows * pr, R * pr, B, C, 1u, K, 0u, pr, K};
             SumJob pcol = {n_cols * pc, C * pc, B, 1u, C, K, n_rows * pr, pc, K * C};
-            hipLaunchKernelGGL(strided_sum_kernel<G>, dim3((unsigned)((((uint64_t)prow.n_out + pcol.n_out) * 2 + 255) / 256)), dim3(256), 0, st, l.buckets, l.parts, prow, pcol, 2u);
+            hipLaunchKernelGGL(strided_sum_kernel<G>, dim3((unsigned)((((uint64_t)prow.n_out + pcol.n_out) * 2 + 255) / 256)), dim3(256), 0, st, buckets, parts, prow, pcol, 2u);
             // step 2: contiguous runs of pr (pc) partial sums
             SumJob frow = {n_rows, n_rows, 0u, pr, 1u, pr, 0u};
             SumJob fcol = {n_cols, n_cols, 0u, pc, 1u, pc, n_rows, 1u, 0u, n_rows * pr};
             const uint32_t lpo2 = 2 * std::min<uint32_t>(32u, std::max(pr, pc) / 2);
-            hipLaunchKernelGGL(strided_sum_kernel<G>, dim3(((n_rows + n_cols) * lpo2 + 255) / 256), dim3(256), 0, st, l.parts, l.rows, frow, fcol, lpo2);
+            hipLaunchKernelGGL(strided_sum_kernel<G>, dim3(((n_rows + n_cols) * lpo2 + 255) / 256), dim3(256), 0, st, parts, row_sums, frow, fcol, lpo2);
         } else {
         // lanes per output (two lanes = one point): many outputs (one bucket set per window) -> 16 pairs each walk
         // count/16 buckets and finish with a 4-level tree; few outputs (shared bucket set) -> 32 pairs, shortest chain
         const uint32_t lpo_env = opt.lanes_per_output;
         const uint32_t lpo = lpo_env ? lpo_env : ((n_rows + n_cols) >= 4096 ? 32u : 64u);
-        hipLaunchKernelGGL(strided_sum_kernel<G>, dim3(((n_rows + n_cols) * lpo + 255) / 256), dim3(256), 0, st, l.buckets, l.rows, rows, cols, lpo);
+        hipLaunchKernelGGL(strided_sum_kernel<G>, dim3(((n_rows + n_cols) * lpo + 255) / 256), dim3(256), 0, st, buckets, row_sums, rows, cols, lpo);
         }
         hipLaunchKernelGGL(weighted_sum_kernel<G>, dim3(groups * (bpr + bpc)), dim3(HS_THREADS), (size_t)HalfRegs<F>::COUNT * HS_THREADS * 4, st,
-                           l.rows, R, groups, l.rows + (size_t)n_rows * XW, C, l.fin);
+                           row_sums, R, groups, row_sums + (size_t)n_rows * XW, C, fin);
         ZK_HIP(hipGetLastError());
-        ZK_HIP(hipMemcpyAsync(h_final, l.fin, (size_t)groups * (bpr + bpc) * 2 * XW * 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(h_final, fin, (size_t)groups * (bpr + bpc) * 2 * XW * 4, hipMemcpyDeviceToHost, st));
         return ZK_OK;
     }
 
@@ -468,7 +457,7 @@ struct MsmPlan : MsmPlanBase {
         const uint64_t v[ZK_MSM_VIEW_SLOTS] = {
             (uint64_t)(uintptr_t)front.digits_buf(), (uint64_t)(uintptr_t)d_bases, (uint64_t)(uintptr_t)own.sorted, (uint64_t)(uintptr_t)own.bstart,
             (uint64_t)(uintptr_t)own.sstart, (uint64_t)(uintptr_t)own.big_list, (uint64_t)(uintptr_t)own.big_count,
-            (uint64_t)(uintptr_t)ws.partials, (uint64_t)(uintptr_t)ws.buckets,
+            (uint64_t)(uintptr_t)ws.partials.as(), (uint64_t)(uintptr_t)ws.buckets.as(),
             n, n_api, (uint64_t)c, (uint64_t)nwin, B, glv ? 1u : 0u, pre ? 1u : 0u, wide ? 1u : 0u, (uint64_t)pw_first, (uint64_t)pw_count,
             (uint64_t)ws.w_first, (uint64_t)ws.w_count, ws.groups, ws.seg_len, q_m, front.view_dstride,
             (uint64_t)front.view_route, (uint64_t)front.view_fine_log, front.view_split_fine() ? 1u : 0u, split_acc ? 1u : 0u};
@@ -695,37 +684,35 @@ static int batch_mul_impl(uint64_t n, const uint64_t* scalars, const uint64_t* b
     typedef typename G::Fr FrP;
     constexpr int AW = 2 * F::LIMBS, XW = 4 * F::LIMBS;
     if (n == 0) return ZK_OK;
-    uint32_t *ds = nullptr, *db = nullptr, *dout = nullptr, *temp = nullptr;
-    int rc = ZK_OK;
+    DevBuf ds, db, dout, temp;
     const bool fixed = broadcast && n >= FIXED_BASE_MIN;
     uint64_t nb = broadcast ? 1 : n;
-    ZK_ALLOC(&ds, n * FrP::W * 4);
-    do {
-        if (dev_alloc_cached((void**)&temp, n * XW * 4) != ZK_OK || dev_alloc_cached((void**)&dout, n * AW * 4) != ZK_OK) { rc = ZK_ERR_HIP; break; }
-        if (hipMemcpy(ds, scalars, n * FrP::W * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed"); break; }
-        if (fixed) {
-            FixedTable<G>& ft = FixedTable<G>::get();
-            std::lock_guard<std::mutex> lock(ft.mu);
-            if ((rc = ft.ensure(bases))) break;
-            FixedBias bias;
-            memset(&bias, 0, sizeof(bias));
-            for (int j = 0; j < ft.nwin; ++j) {
-                int bit = j * FIXED_C + (FIXED_C - 1);
-                bias.v[bit >> 5] |= 1u << (bit & 31);
-            }
-            hipLaunchKernelGGL(fixed_mul_kernel<G>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds, n, ft.d_table, ft.nwin, bias, temp);
-            if (hipDeviceSynchronize() != hipSuccess) { rc = fail(ZK_ERR_HIP, "fixed-base multiplication kernel failed"); break; }
-        } else {
-            if (dev_alloc_cached((void**)&db, nb * AW * 4) != ZK_OK) { rc = ZK_ERR_HIP; break; }
-            if (hipMemcpy(db, bases, nb * AW * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed"); break; }
-            hipLaunchKernelGGL(varbase_mul_kernel<G>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, 0, ds, db, broadcast, n, temp);
+    ZK_HIP_RC(ds.alloc(n * FrP::W * 4));
+    ZK_HIP_RC(temp.alloc(n * XW * 4));
+    ZK_HIP_RC(dout.alloc(n * AW * 4));
+    ZK_HIP(hipMemcpy(ds.as(), scalars, n * FrP::W * 4, hipMemcpyHostToDevice));
+    if (fixed) {
+        FixedTable<G>& ft = FixedTable<G>::get();
+        std::lock_guard<std::mutex> lock(ft.mu);
+        ZK_HIP_RC(ft.ensure(bases));
+        FixedBias bias;
+        memset(&bias, 0, sizeof(bias));
+        for (int j = 0; j < ft.nwin; ++j) {
+            int bit = j * FIXED_C + (FIXED_C - 1);
+            bias.v[bit >> 5] |= 1u << (bit & 31);
         }
-        hipLaunchKernelGGL(normalize_kernel<G>, dim3((unsigned)((n + (uint64_t)NORM_THREADS * NORM_E - 1) / ((uint64_t)NORM_THREADS * NORM_E))),
-                           dim3(NORM_THREADS), 0, 0, temp, n, dout, 1);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, n * AW * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "batch_mul kernel / D2H failed"); break; }
-    } while (0);
-    dev_free_cached(ds); dev_free_cached(db); dev_free_cached(dout); dev_free_cached(temp);
-    return rc;
+        hipLaunchKernelGGL(fixed_mul_kernel<G>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ds.as(), n, ft.d_table.as(), ft.nwin, bias, temp.as());
+        ZK_HIP(hipDeviceSynchronize());
+    } else {
+        ZK_HIP_RC(db.alloc(nb * AW * 4));
+        ZK_HIP(hipMemcpy(db.as(), bases, nb * AW * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(varbase_mul_kernel<G>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, 0, ds.as(), db.as(), broadcast, n, temp.as());
+    }
+    hipLaunchKernelGGL(normalize_kernel<G>, dim3((unsigned)((n + (uint64_t)NORM_THREADS * NORM_E - 1) / ((uint64_t)NORM_THREADS * NORM_E))),
+                       dim3(NORM_THREADS), 0, 0, temp.as(), n, dout.as(), 1);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpy(out, dout.as(), n * AW * 4, hipMemcpyDeviceToHost));
+    return ZK_OK;
 }
 
 // batched (de)compression of n points between host buffers: `to_bytes` != 0 encodes canonical affine rows, 0 decodes.
@@ -736,30 +723,24 @@ static int codec_impl(uint64_t n, const void* in, void* out, int to_bytes, uint6
     constexpr size_t ROW = (size_t)2 * F::LIMBS * 4, ENC = CodecLayout<G>::TOTAL;
     if (n == 0) return ZK_OK;
     const size_t in_bytes = n * (to_bytes ? ROW : ENC), out_bytes = n * (to_bytes ? ENC : ROW);
-    uint8_t *din = nullptr, *dout = nullptr;
-    unsigned long long* derr = nullptr;
-    int rc = ZK_OK;
-    ZK_ALLOC(&din, in_bytes);
-    do {
-        if (dev_alloc_cached((void**)&dout, out_bytes) != ZK_OK || dev_alloc_cached((void**)&derr, 8) != ZK_OK) { rc = ZK_ERR_HIP; break; }
-        unsigned long long first = ~0ull;
-        if (hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(derr, &first, 8, hipMemcpyHostToDevice) != hipSuccess) {
-            rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed");
-            break;
-        }
-        const dim3 grid((unsigned)((n + 127) / 128)), block(128);
-        if (to_bytes) hipLaunchKernelGGL(points_encode_kernel<G>, grid, block, 0, 0, (const uint32_t*)din, n, dout, derr);
-        else hipLaunchKernelGGL(points_decode_kernel<G>, grid, block, 0, 0, (const uint8_t*)din, n, (uint32_t*)dout, derr);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(&first, derr, 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "point codec kernel failed"); break; }
-        if (first != ~0ull) {
-            if (bad_index) *bad_index = (uint64_t)(first >> 8);
-            rc = fail(ZK_ERR_POINT, codec_message((int)(first & 0xFF)));
-            break;
-        }
-        if (hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy D2H failed"); break; }
-    } while (0);
-    dev_free_cached(din); dev_free_cached(dout); dev_free_cached(derr);
-    return rc;
+    DevBuf din, dout, derr;
+    ZK_HIP_RC(din.alloc(in_bytes));
+    ZK_HIP_RC(dout.alloc(out_bytes));
+    ZK_HIP_RC(derr.alloc(8));
+    unsigned long long first = ~0ull;
+    ZK_HIP(hipMemcpy(din.as(), in, in_bytes, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(derr.as(), &first, 8, hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((n + 127) / 128)), block(128);
+    if (to_bytes) hipLaunchKernelGGL(points_encode_kernel<G>, grid, block, 0, 0, din.as<const uint32_t>(), n, dout.as<uint8_t>(), derr.as<unsigned long long>());
+    else hipLaunchKernelGGL(points_decode_kernel<G>, grid, block, 0, 0, din.as<const uint8_t>(), n, dout.as(), derr.as<unsigned long long>());
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpy(&first, derr.as(), 8, hipMemcpyDeviceToHost));
+    if (first != ~0ull) {
+        if (bad_index) *bad_index = (uint64_t)(first >> 8);
+        return fail(ZK_ERR_POINT, codec_message((int)(first & 0xFF)));
+    }
+    ZK_HIP(hipMemcpy(out, dout.as(), out_bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
 }
 
 

@@ -8,16 +8,10 @@
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include "../../include/zkmi.h"
+#include "dev_buf.h"
 #include "msm_front.h"
 
 namespace zkmi {
-
-// a device allocation with shared ownership (the bases / fixed-base table of a plan and its clones)
-void dev_free_cached(void* p);  // common.hip.h / host.hip
-struct DeviceBlock {
-    void* ptr = nullptr;
-    ~DeviceBlock() { dev_free_cached(ptr); }
-};
 
 // what a plan with a run in flight lends to a second plan that multiplies the SAME scalars against other bases of the
 // same length (Groth16: <tau_1, v> in G1 and <tau_2, v> in G2): the digits and the sorted entry list

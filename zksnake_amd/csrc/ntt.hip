@@ -22,6 +22,7 @@
 #include "ntt_lazy.hip.h"
 
 namespace zkmi {
+using mem::DevBuf;
 
 constexpr int NTT_TILE_LOG = 11;   // 2048 elements = 72 KiB of LDS per workgroup (limb-major), two workgroups per CU
 #ifndef NTT_THREADS_N
@@ -468,7 +469,9 @@ static int get_twiddles(int curve, int log_n, TwiddleSet* out, hipStream_t strea
     if (ts.stages > P::TWO_ADICITY) ts.stages = P::TWO_ADICITY;
     const size_t bytes = (((size_t)1 << ts.stages) - 1) * TW_WORDS * 4;
     ZK_HIP(hipMalloc(&ts.fwd, bytes));
-    ZK_HIP(hipMalloc(&ts.inv, bytes));
+    hipError_t e_inv = hipMalloc(&ts.inv, bytes);
+    if (e_inv != hipSuccess) (void)hipFree(ts.fwd);
+    ZK_HIP(e_inv);
     for (int s = 0; s < ts.stages; ++s) {
         const uint32_t count = 1u << s;
         const size_t off = ((size_t)count - 1) * TW_WORDS;
@@ -643,48 +646,40 @@ static int ntt_host_impl(int curve, int inverse, int coset, uint64_t n_in, const
     int log_n = log2_u64(n);
     if (log_n > P::TWO_ADICITY || log_n > 30) return fail(ZK_ERR_DOMAIN, "Domain size is too large");
     const size_t eb = P::W * 4;
-    uint32_t* d = nullptr;
     // An input longer than the domain is TRUNCATED to the domain size: the reference hands the raw slice to
     // EvaluationDomain::fft / ifft (polynomial.rs:541-542,567-568), whose radix-2 fft_in_place / ifft_in_place start with
     // `coeffs.resize(self.size(), zero)` [ark-poly 0.4.2, not vendored: parity unpinned, see DESIGN.md section 2]; only
     // DensePolynomial::evaluate_over_domain folds modulo X^n - 1, and the reference does not call it on this path.
     if (n_in > n) n_in = n;
     const uint64_t alloc = n;
-    ZK_ALLOC(&d, alloc * eb);
-    int rc = ZK_OK;
-    do {
-        if (hipMemset(d, 0, alloc * eb) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemset failed"); break; }
-        if (n_in && hipMemcpy(d, in, n_in * eb, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed"); break; }
-        hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((alloc + 255) / 256)), dim3(256), 0, 0, alloc, d);
-        if (coset && !inverse) { rc = coset_scale_impl<P>(curve, 0, log_n, d, 0); if (rc) break; }
-        rc = ntt_dev_impl<P>(curve, inverse, log_n, d, 0);
-        if (rc) break;
-        if (coset && inverse) { rc = coset_scale_impl<P>(curve, 1, log_n, d, 0); if (rc) break; }
-        if (hipMemcpy(out, d, n * eb, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy D2H failed"); break; }
-    } while (0);
-    dev_free_cached(d);
-    return rc;
+    DevBuf buf;
+    ZK_HIP_RC(buf.alloc(alloc * eb));
+    uint32_t* const d = buf.as();
+    ZK_HIP(hipMemset(d, 0, alloc * eb));
+    if (n_in) ZK_HIP(hipMemcpy(d, in, n_in * eb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((alloc + 255) / 256)), dim3(256), 0, 0, alloc, d);
+    if (coset && !inverse) ZK_HIP_RC(coset_scale_impl<P>(curve, 0, log_n, d, 0));
+    ZK_HIP_RC(ntt_dev_impl<P>(curve, inverse, log_n, d, 0));
+    if (coset && inverse) ZK_HIP_RC(coset_scale_impl<P>(curve, 1, log_n, d, 0));
+    ZK_HIP(hipMemcpy(out, d, n * eb, hipMemcpyDeviceToHost));
+    return ZK_OK;
 }
 
 template <class P>
 static int vec_op_host_impl(int op, uint64_t size, uint64_t n_a, const uint64_t* a, uint64_t n_b, const uint64_t* b, uint64_t* out) {
     if (size == 0) return ZK_OK;
     const size_t eb = P::W * 4;
-    uint32_t* d = nullptr;
-    ZK_ALLOC(&d, 2 * size * eb);
-    int rc = ZK_OK;
-    do {
-        if (hipMemset(d, 0, 2 * size * eb) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemset failed"); break; }
-        uint64_t ca = n_a < size ? n_a : size, cb = n_b < size ? n_b : size;
-        if (ca && hipMemcpy(d, a, ca * eb, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed"); break; }
-        if (cb && hipMemcpy(d + size * P::W, b, cb * eb, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed"); break; }
-        hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((2 * size + 255) / 256)), dim3(256), 0, 0, 2 * size, d);
-        rc = vec_op_dev_impl<P>(op, size, d, d + size * P::W, d, 0);
-        if (rc) break;
-        if (hipMemcpy(out, d, size * eb, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy D2H failed"); break; }
-    } while (0);
-    dev_free_cached(d);
-    return rc;
+    DevBuf buf;
+    ZK_HIP_RC(buf.alloc(2 * size * eb));
+    uint32_t* const d = buf.as();
+    ZK_HIP(hipMemset(d, 0, 2 * size * eb));
+    uint64_t ca = n_a < size ? n_a : size, cb = n_b < size ? n_b : size;
+    if (ca) ZK_HIP(hipMemcpy(d, a, ca * eb, hipMemcpyHostToDevice));
+    if (cb) ZK_HIP(hipMemcpy(d + size * P::W, b, cb * eb, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((2 * size + 255) / 256)), dim3(256), 0, 0, 2 * size, d);
+    ZK_HIP_RC(vec_op_dev_impl<P>(op, size, d, d + size * P::W, d, 0));
+    ZK_HIP(hipMemcpy(out, d, size * eb, hipMemcpyDeviceToHost));
+    return ZK_OK;
 }
 
 template <class P>
@@ -694,26 +689,22 @@ static int div_vanishing_host_impl(uint64_t n, uint64_t len, const uint64_t* coe
     if (len == 0) return ZK_OK;
     const size_t eb = P::W * 4;
     uint64_t qlen = len > n ? len - n : 0, top = len < n ? len : n;
-    uint32_t *dc = nullptr, *dq = nullptr, *dr = nullptr;
-    int* dflag = nullptr;
-    ZK_ALLOC(&dc, len * eb);
-    int rc = ZK_OK;
-    do {
-        if (dev_alloc_cached((void**)&dq, (qlen ? qlen : 1) * eb) != ZK_OK || dev_alloc_cached((void**)&dr, top * eb) != ZK_OK ||
-            dev_alloc_cached((void**)&dflag, sizeof(int)) != ZK_OK) { rc = fail(ZK_ERR_HIP, "hipMalloc failed"); break; }
-        if (hipMemcpy(dc, coeffs, len * eb, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy H2D failed"); break; }
-        (void)hipMemset(dflag, 0, sizeof(int));
-        hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, 0, len, dc);
-        uint64_t lim = qlen > top ? qlen : top;
-        hipLaunchKernelGGL(div_vanishing_kernel<P>, dim3((unsigned)((lim + 255) / 256)), dim3(256), 0, 0, n, len, dc, dq, dr, dflag);
-        int flag = 0;
-        if (hipMemcpy(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy D2H failed"); break; }
-        if (qlen && hipMemcpy(q, dq, qlen * eb, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy D2H failed"); break; }
-        if (hipMemcpy(rem, dr, top * eb, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemcpy D2H failed"); break; }
-        *rem_is_zero = flag ? 0 : 1;
-    } while (0);
-    dev_free_cached(dc); dev_free_cached(dq); dev_free_cached(dr); dev_free_cached(dflag);
-    return rc;
+    DevBuf dc, dq, dr, dflag;
+    ZK_HIP_RC(dc.alloc(len * eb));
+    ZK_HIP_RC(dq.alloc((qlen ? qlen : 1) * eb));
+    ZK_HIP_RC(dr.alloc(top * eb));
+    ZK_HIP_RC(dflag.alloc(sizeof(int)));
+    ZK_HIP(hipMemcpy(dc.as(), coeffs, len * eb, hipMemcpyHostToDevice));
+    (void)hipMemset(dflag.as(), 0, sizeof(int));
+    hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, 0, len, dc.as());
+    uint64_t lim = qlen > top ? qlen : top;
+    hipLaunchKernelGGL(div_vanishing_kernel<P>, dim3((unsigned)((lim + 255) / 256)), dim3(256), 0, 0, n, len, dc.as(), dq.as(), dr.as(), dflag.as<int>());
+    int flag = 0;
+    ZK_HIP(hipMemcpy(&flag, dflag.as(), sizeof(int), hipMemcpyDeviceToHost));
+    if (qlen) ZK_HIP(hipMemcpy(q, dq.as(), qlen * eb, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(rem, dr.as(), top * eb, hipMemcpyDeviceToHost));
+    *rem_is_zero = flag ? 0 : 1;
+    return ZK_OK;
 }
 
 // ---- QAP quotient on a coset ------------------------------------------------------------------------------------
@@ -759,7 +750,9 @@ static int get_qap_tabs(int curve, int log_n, QapTabs* out, hipStream_t stream) 
     const uint64_t n = 1ull << log_n;
     QapTabs t;
     ZK_HIP(hipMalloc(&t.fwd, n * P::W * 4));
-    ZK_HIP(hipMalloc(&t.inv, n * P::W * 4));
+    hipError_t e_inv = hipMalloc(&t.inv, n * P::W * 4);
+    if (e_inv != hipSuccess) (void)hipFree(t.fwd);
+    ZK_HIP(e_inv);
     uint32_t nn[P::W] = {0};
     nn[0] = (uint32_t)n;
     const Fp<P> inv_n = fp_inv<P>(fp_from_canonical<P>(nn));                            // R / N

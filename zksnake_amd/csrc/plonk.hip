@@ -17,6 +17,7 @@
 #include "fr_mem.hip.h"
 
 namespace zkmi {
+using mem::DevBuf;
 
 template <class P>
 __host__ Fp<P> scalar_in(const uint64_t* s) {
@@ -318,31 +319,27 @@ static int inclusive_scan(uint64_t n, int reverse, const uint32_t* in, uint32_t*
 template <class P>
 static int grand_product_dev_impl(uint64_t n, const void* num, const void* den, void* out, hipStream_t st) {
     const size_t eb = P::W * 4;
-    uint32_t* work = nullptr;  // PN (n+1) | SD (n+1) | partials
-    ZK_ALLOC(&work, (2 * (n + 1) + SCAN_MAX_PARTIALS) * eb);
+    DevBuf work_buf;  // PN (n+1) | SD (n+1) | partials
+    ZK_HIP_RC(work_buf.alloc((2 * (n + 1) + SCAN_MAX_PARTIALS) * eb));
+    uint32_t* const work = work_buf.as();
     uint32_t *pn = work, *sd = work + (n + 1) * P::W, *partial = work + 2 * (n + 1) * P::W;
-    int rc = ZK_OK;
-    do {
-        uint32_t one_m[P::W], dtot[P::W];
-        fp_pack<P>(one_m, fp_reduce_full<P>(fp_one<P>()));
-        if (hipMemcpyAsync(pn, one_m, eb, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(sd + n * P::W, one_m, eb, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail(ZK_ERR_HIP, "grand product: upload failed"); break; }
-        if ((rc = inclusive_scan<P, ScanMul>(n, 0, (const uint32_t*)num, pn + P::W, partial, st))) break;
-        if ((rc = inclusive_scan<P, ScanMul>(n, 1, (const uint32_t*)den, sd, partial, st))) break;
-        if (hipMemcpyAsync(dtot, sd, eb, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            rc = fail(ZK_ERR_HIP, "grand product: copy back failed");
-            break;
-        }
-        Fp<P> d = fp_unpack<P>(dtot);  // product of all denominators, Montgomery
-        if (fp_is_zero<P>(d)) { rc = fail(ZK_ERR_ARG, "grand product: zero denominator"); break; }
-        Fp<P> one_raw = fp_zero<P>();
-        one_raw.v[0] = 1;
-        Fp<P> dinv = fp_reduce_full<P>(fp_mul<P>(fp_inv<P>(d), one_raw));  // canonical integer 1 / Dtot
-        hipLaunchKernelGGL(grand_product_finish_kernel<P>, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, n + 1, pn, sd, dinv, (uint32_t*)out);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = fail(ZK_ERR_HIP, "grand product: finish failed");
-    } while (0);
-    dev_free_cached(work);
-    return rc;
+    uint32_t one_m[P::W], dtot[P::W];
+    fp_pack<P>(one_m, fp_reduce_full<P>(fp_one<P>()));
+    ZK_HIP(hipMemcpyAsync(pn, one_m, eb, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(sd + n * P::W, one_m, eb, hipMemcpyHostToDevice, st));
+    ZK_HIP_RC((inclusive_scan<P, ScanMul>(n, 0, (const uint32_t*)num, pn + P::W, partial, st)));
+    ZK_HIP_RC((inclusive_scan<P, ScanMul>(n, 1, (const uint32_t*)den, sd, partial, st)));
+    ZK_HIP(hipMemcpyAsync(dtot, sd, eb, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    Fp<P> d = fp_unpack<P>(dtot);  // product of all denominators, Montgomery
+    if (fp_is_zero<P>(d)) return fail(ZK_ERR_ARG, "grand product: zero denominator");
+    Fp<P> one_raw = fp_zero<P>();
+    one_raw.v[0] = 1;
+    Fp<P> dinv = fp_reduce_full<P>(fp_mul<P>(fp_inv<P>(d), one_raw));  // canonical integer 1 / Dtot
+    hipLaunchKernelGGL(grand_product_finish_kernel<P>, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, n + 1, pn, sd, dinv, (uint32_t*)out);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
 }
 
 // coeffs (n) = q (n - 1) * (X - root) + rem:  b_k = c_k root^k, SS_j = sum_{k >= j} b_k, q_j = SS_{j+1} root^-(j+1), rem = SS_0
@@ -359,25 +356,23 @@ static int div_linear_dev_impl(uint64_t n, const void* coeffs, const uint64_t* r
         ZK_HIP(hipStreamSynchronize(st));
         return ZK_OK;
     }
-    uint32_t* work = nullptr;  // b / SS (n) | partials
-    ZK_ALLOC(&work, (n + SCAN_MAX_PARTIALS) * eb);
+    DevBuf work_buf;  // b / SS (n) | partials
+    ZK_HIP_RC(work_buf.alloc((n + SCAN_MAX_PARTIALS) * eb));
+    uint32_t* const work = work_buf.as();
     uint32_t* partial = work + n * P::W;
-    int rc = ZK_OK;
-    do {
-        const uint32_t chunk = 16;
-        const unsigned blocks = (unsigned)(((n + chunk - 1) / chunk + 255) / 256);
-        hipLaunchKernelGGL(geom_scale_kernel<P>, dim3(blocks), dim3(256), 0, st, n, chunk, (const uint32_t*)coeffs, fp_one<P>(), root_m, work);
-        if ((rc = inclusive_scan<P, ScanAdd>(n, 1, work, work, partial, st))) break;
-        if (hipMemcpyAsync(r, work, eb, hipMemcpyDeviceToHost, st) != hipSuccess) { rc = fail(ZK_ERR_HIP, "div_linear: copy back failed"); break; }
-        if (n > 1) {
-            Fp<P> rinv_m = fp_inv<P>(root_m);
-            const unsigned qb = (unsigned)(((n - 1 + chunk - 1) / chunk + 255) / 256);
-            hipLaunchKernelGGL(geom_scale_kernel<P>, dim3(qb), dim3(256), 0, st, n - 1, chunk, work + P::W, rinv_m, rinv_m, (uint32_t*)q);
-        }
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = fail(ZK_ERR_HIP, "div_linear: kernel failed");
-    } while (0);
-    dev_free_cached(work);
-    return rc;
+    const uint32_t chunk = 16;
+    const unsigned blocks = (unsigned)(((n + chunk - 1) / chunk + 255) / 256);
+    hipLaunchKernelGGL(geom_scale_kernel<P>, dim3(blocks), dim3(256), 0, st, n, chunk, (const uint32_t*)coeffs, fp_one<P>(), root_m, work);
+    ZK_HIP_RC((inclusive_scan<P, ScanAdd>(n, 1, work, work, partial, st)));
+    ZK_HIP(hipMemcpyAsync(r, work, eb, hipMemcpyDeviceToHost, st));
+    if (n > 1) {
+        Fp<P> rinv_m = fp_inv<P>(root_m);
+        const unsigned qb = (unsigned)(((n - 1 + chunk - 1) / chunk + 255) / 256);
+        hipLaunchKernelGGL(geom_scale_kernel<P>, dim3(qb), dim3(256), 0, st, n - 1, chunk, work + P::W, rinv_m, rinv_m, (uint32_t*)q);
+    }
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
 }
 
 // ---- host wrappers ------------------------------------------------------------------------------------
@@ -427,19 +422,16 @@ template <class P>
 static int is_zero_impl(uint64_t n, const void* x, int* is_zero, hipStream_t st) {
     *is_zero = 1;
     if (n == 0) return ZK_OK;
-    int* dflag = nullptr;
-    ZK_ALLOC(&dflag, sizeof(int));
-    int flag = 0, rc = ZK_OK;
-    do {
-        if (hipMemsetAsync(dflag, 0, sizeof(int), st) != hipSuccess) { rc = fail(ZK_ERR_HIP, "hipMemsetAsync failed"); break; }
-        uint64_t nv = n * (P::W / 4);
-        hipLaunchKernelGGL(is_zero_kernel<P>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, nv, (const uint4*)x, dflag);
-        if (hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = fail(ZK_ERR_HIP, "is_zero: copy back failed"); break; }
-    } while (0);
-    dev_free_cached(dflag);
+    DevBuf dflag;
+    ZK_HIP_RC(dflag.alloc(sizeof(int)));
+    int flag = 0;
+    ZK_HIP(hipMemsetAsync(dflag.as(), 0, sizeof(int), st));
+    uint64_t nv = n * (P::W / 4);
+    hipLaunchKernelGGL(is_zero_kernel<P>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, nv, (const uint4*)x, dflag.as<int>());
+    ZK_HIP(hipMemcpyAsync(&flag, dflag.as(), sizeof(int), hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
     *is_zero = flag ? 0 : 1;
-    return rc;
+    return ZK_OK;
 }
 
 template <class P>
@@ -484,17 +476,14 @@ static int poly_eval_impl_dev(uint64_t n, const void* coeffs, const uint64_t* x,
     const uint32_t chunk = 32;
     uint64_t threads = (n + chunk - 1) / chunk;
     unsigned blocks = (unsigned)((threads + 255) / 256);
-    uint32_t* dpart = nullptr;
-    ZK_ALLOC(&dpart, (size_t)blocks * P::W * 4);
+    DevBuf dpart;
+    ZK_HIP_RC(dpart.alloc((size_t)blocks * P::W * 4));
     std::vector<uint32_t> part((size_t)blocks * P::W);
-    int rc = ZK_OK;
     hipLaunchKernelGGL(poly_eval_kernel<P>, dim3(blocks), dim3(256), 0, st, n, chunk, (const uint32_t*)coeffs,
-                       fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(x)), dpart);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(part.data(), dpart, part.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        rc = fail(ZK_ERR_HIP, "poly_eval: kernel or copy back failed");
-    dev_free_cached(dpart);
-    if (rc) return rc;
+                       fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(x)), dpart.as());
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(part.data(), dpart.as(), part.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
     Fp<P> acc = fp_zero<P>();
     for (unsigned b = 0; b < blocks; ++b) acc = fp_add<P>(acc, fp_unpack<P>(part.data() + (size_t)b * P::W));
     fp_pack<P>(o, fp_reduce_full<P>(acc));
@@ -514,19 +503,16 @@ static int poly_eval_many_impl(int k, const uint64_t* counts, const void* const*
     }
     for (int i = 0; i < k * P::W / 2; ++i) outs[i] = 0;
     if (total == 0) return ZK_OK;
-    uint32_t* dpart = nullptr;
-    ZK_ALLOC(&dpart, (size_t)total * P::W * 4);
+    DevBuf dpart;
+    ZK_HIP_RC(dpart.alloc((size_t)total * P::W * 4));
     std::vector<uint32_t> part((size_t)total * P::W);
-    int rc = ZK_OK;
     for (int i = 0; i < k; ++i)
         if (counts[i])
             hipLaunchKernelGGL(poly_eval_kernel<P>, dim3(blocks[i]), dim3(256), 0, st, counts[i], chunk, (const uint32_t*)coeffs[i],
-                               fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(xs + (size_t)i * (P::W / 2))), dpart + (size_t)first[i] * P::W);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(part.data(), dpart, part.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        rc = fail(ZK_ERR_HIP, "poly_eval: kernel or copy back failed");
-    dev_free_cached(dpart);
-    if (rc) return rc;
+                               fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(xs + (size_t)i * (P::W / 2))), dpart.as() + (size_t)first[i] * P::W);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(part.data(), dpart.as(), part.size() * 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < k; ++i) {
         Fp<P> acc = fp_zero<P>();
         for (unsigned b = 0; b < blocks[i]; ++b) acc = fp_add<P>(acc, fp_unpack<P>(part.data() + (size_t)(first[i] + b) * P::W));
