@@ -434,6 +434,40 @@ int zk_sumcheck_round_dev(int curve, int log_n, int n_tables, const void* const*
                           const int* term_deg, const int* term_tables, const uint64_t* r, void* const* d_tables_out, uint64_t* s_out,
                           void* stream);
 
+/* ---- inner-product argument, scalar side (csrc/ipa.hip) ---------------------------------------------------------------
+ * The Bulletproofs halving argument of subprotocol/bulletproofs/ipa.py WITHOUT folding the generators.  n = 2^log_n,
+ * 0 <= log_n <= ZK_IPA_MAX_LOG.  After k rounds with challenges u_0 .. u_(k-1) the reference's folded generators are
+ *   G^(k)_j = sum_{i = j mod m} s_i G_i,  H^(k)_j = sum_{i = j mod m} s_i^-1 H_i,  m = n >> k,
+ *   s_i = prod_{t<k} (bit (log_n-1-t) of i ? u_t : u_t^-1)       (the verifier's s vector once k = log_n),
+ * so L_k and R_k are MSMs over the ORIGINAL G || H (2n bases, one plan for a whole proof) with the scalars written here.
+ * All vectors are canonical Fr elements in device memory; challenges are canonical 4-limb integers in host memory, reduced
+ * on entry when >= r.  Workgroups of 256 threads on a grid capped at 1024 workgroups: the pass over i < n takes a second item
+ * per thread first at n = 2^19, the fold (m items) and the cross products (m/2 items) first at n = 2^20.
+ * ZK_ERR_ARG for a null pointer, sizes out of range, a challenge missing or present against the rules below, or two buffers
+ * that overlap; nothing is written then. */
+#define ZK_IPA_MAX_LOG 22
+/* Round k of the prover, 0 <= k <= log_n; m = n >> k, h = m / 2.  d_a, d_b: n elements, of which the first 2m are live on
+ * entry (n when k = 0) and the first m afterwards; d_s, d_s_inv: n elements; d_scal_L, d_scal_R: 2n elements each.
+ * Step 1.  k = 0: u and u_inv must be NULL; s[i] = s_inv[i] = 1.  k >= 1: u, u_inv (4 limbs each) are the challenge of round
+ *   k-1 and its inverse (u * u_inv = 1 is not checked); in place for j < m
+ *     a[j] = u a[j] + u_inv a[j+m],   b[j] = u_inv b[j] + u b[j+m],
+ *   then for i < n with bit = (i >> (log_n - k)) & 1:  s[i] *= bit ? u : u_inv,  s_inv[i] *= bit ? u_inv : u.
+ * Step 2 (k < log_n only), for i < n with j = i mod m:
+ *     j >= h:  scal_L[i] = a[j-h] s[i],  scal_R[n+i] = b[j-h] s_inv[i],  scal_L[n+i] = scal_R[i] = 0
+ *     j <  h:  scal_L[n+i] = b[j+h] s_inv[i],  scal_R[i] = a[j+h] s[i],  scal_L[i] = scal_R[n+i] = 0
+ *   (every element of d_scal_L, d_scal_R is written, zeros included), so that
+ *     L_k = <scal_L, G || H> + cross[0..3] Q,   R_k = <scal_R, G || H> + cross[4..7] Q,
+ *     cross[0..3] = sum_{j<h} a[j] b[j+h],   cross[4..7] = sum_{j<h} a[j+h] b[j]   (host, canonical; fixed-order sums).
+ * With k == log_n only step 1 runs: d_scal_L, d_scal_R and cross may be NULL and are not touched; a[0], b[0] are the proof's
+ * scalars.  Synchronises the stream when it returns cross (k < log_n), otherwise it only enqueues. */
+int zk_ipa_round_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const uint64_t* u,
+                     const uint64_t* u_inv, void* d_scal_L, void* d_scal_R, uint64_t* cross, void* stream);
+/* The verifier's scalars (ipa.py:189-198) for the proof's a, b (4 limbs each, host) and the challenges u, u_inv (log_n * 4 limbs
+ * each, host; may be NULL when log_n = 0): d_out[i] = a s_i, d_out[n+i] = b s_i^-1 for i < n, 2n elements, log_n products per
+ * element.  log_n = 0 gives [a, b].  Enqueues only. */
+int zk_ipa_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a, const uint64_t* b,
+                              void* d_out, void* stream);
+
 /* Dense-polynomial helpers over Fr used by the PlonK prover (python/zksnake/plonk/protocol.py:157-484); canonical
  * coefficients, lowest degree first, host memory.  They replace Polynomial.__call__ (src/bn254/polynomial.rs:491-516),
  * Polynomial.__truediv__ by a linear factor (:404-438), the batch_modinv + accumulator loop of protocol.py:296-307 and

@@ -14,6 +14,7 @@ run)
     cd $R
     ZKMI_LIB=$R/build/variants/libzkmi_stock.so timeout -k 10 900 python -m pytest tests/test_gpu_msm.py tests/test_gpu_ntt.py tests/test_gpu_codec.py \
         "tests/test_gpu_groth16.py::test_proof_bytes_equal_closed_form" "tests/test_gpu_groth16.py::test_full_size_proof_equals_committed_closed_form" \
+        tests/test_gpu_ipa_kernels.py tests/test_gpu_ipa.py \
         tests/test_gpu_plonk.py -x -q -m gpu > gpurun_out/stock_pytest.log 2>&1
     timeout -k 10 100 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > gpurun_out/stock_bench_default_build.json 2>/dev/null
     ZKMI_LIB=$R/build/variants/libzkmi_stock.so timeout -k 10 100 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > gpurun_out/stock_bench_stock_build.json 2>/dev/null

@@ -38,6 +38,7 @@ MSM_VIEW_SLOTS = 29
 MSM_VIEW_ROUTE = 25
 MSM_ROUTE_RANGED, MSM_ROUTE_ONE_LEVEL, MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL = 1, 2, 3, 4, 5
 MSM_ROUTES_TWO_LEVEL = (MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL)
+IPA_MAX_LOG = 22  # ZK_IPA_MAX_LOG: an inner-product argument has at most 2^22 elements per vector
 MLE_TILE_LOG = 8  # ZK_MLE_TILE_LOG: variables one launch of the multilinear kernels folds per 256-element tile
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -133,6 +134,8 @@ SIGNATURES = {
     "zk_mle_permute_dev": (_i, [_i, _i, _vp, _u8p, _vp, _vp]),
     "zk_sumcheck_round_dev": (_i, [_i, _i, _i, ctypes.POINTER(_vp), _i, _u64p, ctypes.POINTER(_i), ctypes.POINTER(_i), _u64p,
                                    ctypes.POINTER(_vp), _u64p, _vp]),
+    "zk_ipa_round_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _u64p, _u64p, _vp, _vp, _u64p, _vp]),
+    "zk_ipa_verify_scalars_dev": (_i, [_i, _i, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
     "zk_fr_poly_eval": (_i, [_i, _u64, _u64p, _u64p, _u64p]),
     "zk_fr_poly_div_linear": (_i, [_i, _u64, _u64p, _u64p, _u64p, _u64p]),
     "zk_fr_grand_product": (_i, [_i, _u64, _u64p, _u64p, _u64p]),

@@ -1,0 +1,207 @@
+// ipa.hip -- the scalar side of the Bulletproofs inner-product argument over BN254 Fr / BLS12-381 Fr (gfx950).
+//
+// Stands in for the per-round list arithmetic of InnerProductArgument.prove / .verify
+// (python/zksnake/subprotocol/bulletproofs/ipa.py:105-145, :178-198).  The reference folds the generators every round,
+// G' = u^-1 G_lo + u G_hi; here they are never folded.  With s_i = prod_{t<k} (bit (log_n-1-t) of i ? u_t : u_t^-1) the
+// folded generator is G^(k)_j = sum_{i = j mod m} s_i G_i (and H^(k)_j the same with s_i^-1), so every L_k, R_k is an MSM
+// over the ORIGINAL G || H whose scalars this file writes: one MSM plan serves the commitment, every round and the verifier.
+//
+// Like mle.hip the kernels multiply canonical data by scalars carried in Montgomery form (mont(x, s R) = x s), so no
+// vector is ever converted; a product of two canonical values is closed with R^2.  Workgroups of MLE_TILE threads, the
+// grid capped at IPA_MAX_BLOCKS workgroups; the cross products are per-workgroup partial sums added by one workgroup.
+#include <algorithm>
+#include "common.hip.h"
+#include "fr_mem.hip.h"
+#include "fr_sum.hip.h"
+
+namespace zkmi {
+using mem::DevBuf;
+
+constexpr int IPA_MAX_LOG = ZK_IPA_MAX_LOG;
+constexpr unsigned IPA_MAX_BLOCKS = 1024;   // the grid's cap (mle.hip's): 2^18 threads, so a pass over 2^19 items strides
+
+template <class P>
+struct IpaChallenge {
+    Fp<P> u_m, ui_m;  // u R and u^-1 R
+};
+
+// the integer 1 (not Montgomery form): the canonical one in memory, and mont(x R, 1) = x
+template <class P>
+ZK_HD Fp<P> fp_raw_one() {
+    Fp<P> o = fp_zero<P>();
+    o.v[0] = 1;
+    return o;
+}
+
+// in place, j < m: a[j] = u a[j] + u^-1 a[j+m], b[j] = u^-1 b[j] + u b[j+m].  Element j is read and written by one thread only,
+// element j+m only read.
+template <class P>
+__global__ __launch_bounds__(MLE_TILE) void ipa_fold_kernel(uint64_t m, IpaChallenge<P> c, uint32_t* a, uint32_t* b) {
+    const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
+    for (uint64_t j = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; j < m; j += stride) {
+        const Fp<P> a_lo = load_fr<P>(a + j * P::W), a_hi = load_fr<P>(a + (j + m) * P::W);
+        store_fr<P>(a + j * P::W, fp_reduce_full<P>(fp_add<P>(fp_mul<P>(a_lo, c.u_m), fp_mul<P>(a_hi, c.ui_m))));
+        const Fp<P> b_lo = load_fr<P>(b + j * P::W), b_hi = load_fr<P>(b + (j + m) * P::W);
+        store_fr<P>(b + j * P::W, fp_reduce_full<P>(fp_add<P>(fp_mul<P>(b_lo, c.ui_m), fp_mul<P>(b_hi, c.u_m))));
+    }
+}
+
+// i < n: s[i], s_inv[i] take the challenge of the round before (init: they become 1), and -- write != 0, m >= 2 live elements of
+// a, b -- the 2n scalars of L and of R are written, zeros included.  With j = i mod m, h = m / 2 the partner of j is j ^ h.
+template <class P>
+__global__ __launch_bounds__(MLE_TILE) void ipa_scalars_kernel(uint64_t n, uint64_t m, int shift, int init, int write, IpaChallenge<P> c,
+                                                               const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                               uint32_t* __restrict__ s, uint32_t* __restrict__ s_inv,
+                                                               uint32_t* __restrict__ scal_l, uint32_t* __restrict__ scal_r) {
+    const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
+    const Fp<P> r2 = fp_const<P>(P::R2), zero = fp_zero<P>();
+    for (uint64_t i = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; i < n; i += stride) {
+        Fp<P> sv, si;
+        if (init) {
+            sv = si = fp_raw_one<P>();
+        } else {
+            const bool bit = (i >> shift) & 1;
+            sv = fp_reduce_full<P>(fp_mul<P>(load_fr<P>(s + i * P::W), bit ? c.u_m : c.ui_m));
+            si = fp_reduce_full<P>(fp_mul<P>(load_fr<P>(s_inv + i * P::W), bit ? c.ui_m : c.u_m));
+        }
+        store_fr<P>(s + i * P::W, sv);
+        store_fr<P>(s_inv + i * P::W, si);
+        if (!write) continue;
+        const uint64_t h = m >> 1, j = i & (m - 1), p = j ^ h;
+        const bool upper = (j & h) != 0;
+        const Fp<P> pa = fp_reduce_full<P>(fp_mul<P>(load_fr<P>(a + p * P::W), fp_mul<P>(sv, r2)));
+        const Fp<P> pb = fp_reduce_full<P>(fp_mul<P>(load_fr<P>(b + p * P::W), fp_mul<P>(si, r2)));
+        store_fr<P>(scal_l + i * P::W, upper ? pa : zero);        // a_lo against G_hi
+        store_fr<P>(scal_l + (n + i) * P::W, upper ? zero : pb);  // b_hi against H_lo
+        store_fr<P>(scal_r + i * P::W, upper ? zero : pa);        // a_hi against G_lo
+        store_fr<P>(scal_r + (n + i) * P::W, upper ? pb : zero);  // b_lo against H_hi
+    }
+}
+
+// partial[2 blk] = sum a[j] b[j+h], partial[2 blk + 1] = sum a[j+h] b[j] over the workgroup's j < h
+template <class P>
+__global__ __launch_bounds__(MLE_TILE) void ipa_cross_kernel(uint64_t h, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                             uint32_t* __restrict__ partial) {
+    __shared__ uint32_t lds[P::N][MLE_TILE];
+    Fp<P> cl = fp_zero<P>(), cr = cl;
+    const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
+    for (uint64_t j = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; j < h; j += stride) {
+        cl = fp_add<P>(cl, fp_mul<P>(load_fr<P>(a + j * P::W), load_fr<P>(b + (j + h) * P::W)));
+        cr = fp_add<P>(cr, fp_mul<P>(load_fr<P>(a + (j + h) * P::W), load_fr<P>(b + j * P::W)));
+    }
+    const Fp<P> r2 = fp_const<P>(P::R2);   // every term carries R^-1: closed once per thread
+    uint32_t* dst = partial + (size_t)blockIdx.x * 2 * P::W;
+    block_sum_store<P>(fp_mul<P>(cl, r2), lds, dst);
+    block_sum_store<P>(fp_mul<P>(cr, r2), lds, dst + P::W);
+}
+
+template <class P>
+struct IpaVerifyArgs {
+    Fp<P> u_m[IPA_MAX_LOG], ui_m[IPA_MAX_LOG];  // u_t R, u_t^-1 R
+    Fp<P> a, b;                                 // the proof's scalars, below 2r
+};
+
+// out[i] = a s_i, out[n+i] = b s_i^-1: log_n products each, the chain starting at the canonical a (b)
+template <class P>
+__global__ __launch_bounds__(MLE_TILE) void ipa_verify_scalars_kernel(uint64_t n, int log_n, IpaVerifyArgs<P> v, uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
+    for (uint64_t i = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; i < n; i += stride) {
+        Fp<P> sa = v.a, sb = v.b;
+        for (int t = 0; t < log_n; ++t) {
+            const bool bit = (i >> (log_n - 1 - t)) & 1;
+            sa = fp_mul<P>(sa, bit ? v.u_m[t] : v.ui_m[t]);
+            sb = fp_mul<P>(sb, bit ? v.ui_m[t] : v.u_m[t]);
+        }
+        store_fr<P>(out + i * P::W, fp_reduce_full<P>(sa));
+        store_fr<P>(out + (n + i) * P::W, fp_reduce_full<P>(sb));
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+
+static unsigned ipa_blocks(uint64_t items) {
+    return (unsigned)std::min<uint64_t>((items + MLE_TILE - 1) / MLE_TILE, IPA_MAX_BLOCKS);
+}
+
+template <class P>
+static int ipa_round_impl(int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const uint64_t* u, const uint64_t* u_inv,
+                          void* d_scal_l, void* d_scal_r, uint64_t* cross, hipStream_t st) {
+    if (log_n < 0 || log_n > IPA_MAX_LOG || k < 0 || k > log_n) return fail(ZK_ERR_ARG, "ipa_round: need 0 <= k <= log_n <= 22");
+    if (!d_a || !d_b || !d_s || !d_s_inv) return fail(ZK_ERR_ARG, "ipa_round: null vector");
+    if (k == 0 ? (u || u_inv) : (!u || !u_inv)) return fail(ZK_ERR_ARG, "ipa_round: a challenge goes with every round but the first, and only those");
+    const bool write = k < log_n;
+    if (write && (!d_scal_l || !d_scal_r || !cross)) return fail(ZK_ERR_ARG, "ipa_round: null output");
+    const uint64_t eb = P::W * 4, n = 1ull << log_n, m = n >> k;
+    const void* buf[6] = {d_a, d_b, d_s, d_s_inv, write ? d_scal_l : nullptr, write ? d_scal_r : nullptr};
+    const uint64_t len[6] = {n * eb, n * eb, n * eb, n * eb, 2 * n * eb, 2 * n * eb};
+    for (int x = 0; x < 6; ++x)
+        for (int y = 0; y < x; ++y)
+            if (buf[x] && buf[y] && ranges_overlap(buf[x], len[x], buf[y], len[y])) return fail(ZK_ERR_ARG, "ipa_round: two buffers overlap");
+
+    IpaChallenge<P> c;
+    c.u_m = c.ui_m = fp_zero<P>();
+    if (k) {
+        c.u_m = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u));
+        c.ui_m = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u_inv));
+        hipLaunchKernelGGL(ipa_fold_kernel<P>, dim3(ipa_blocks(m)), dim3(MLE_TILE), 0, st, m, c, (uint32_t*)d_a, (uint32_t*)d_b);
+        ZK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ipa_scalars_kernel<P>, dim3(ipa_blocks(n)), dim3(MLE_TILE), 0, st, n, m, log_n - k, k == 0 ? 1 : 0, write ? 1 : 0, c,
+                       (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_s, (uint32_t*)d_s_inv, (uint32_t*)d_scal_l, (uint32_t*)d_scal_r);
+    ZK_HIP(hipGetLastError());
+    if (!write) return ZK_OK;
+
+    const uint64_t h = m >> 1;
+    const unsigned blocks = ipa_blocks(h);
+    DevBuf part_buf;   // blocks x 2 partial sums | the 2 results
+    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * 2 * eb));
+    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * 2 * P::W;
+    hipLaunchKernelGGL(ipa_cross_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, h, (const uint32_t*)d_a, (const uint32_t*)d_b, part);
+    hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 2, part, res);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(cross, res, 2 * eb, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+}
+
+template <class P>
+static int ipa_verify_scalars_impl(int log_n, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a, const uint64_t* b, void* d_out,
+                                   hipStream_t st) {
+    if (log_n < 0 || log_n > IPA_MAX_LOG) return fail(ZK_ERR_ARG, "ipa_verify_scalars: need 0 <= log_n <= 22");
+    if (!a || !b || !d_out || (log_n && (!u || !u_inv))) return fail(ZK_ERR_ARG, "ipa_verify_scalars: null argument");
+    IpaVerifyArgs<P> v;
+    const Fp<P> one = fp_raw_one<P>();
+    for (int t = 0; t < IPA_MAX_LOG; ++t) {
+        v.u_m[t] = t < log_n ? fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u + 4 * t)) : fp_zero<P>();
+        v.ui_m[t] = t < log_n ? fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u_inv + 4 * t)) : fp_zero<P>();
+    }
+    // mont(x R, 1) = x mod r, below 2r: the start of a chain of products
+    v.a = fp_mul<P>(fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(a)), one);
+    v.b = fp_mul<P>(fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(b)), one);
+    const uint64_t n = 1ull << log_n;
+    hipLaunchKernelGGL(ipa_verify_scalars_kernel<P>, dim3(ipa_blocks(n)), dim3(MLE_TILE), 0, st, n, log_n, v, (uint32_t*)d_out);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+}  // namespace zkmi
+
+using namespace zkmi;
+
+extern "C" {
+
+int zk_ipa_round_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const uint64_t* u, const uint64_t* u_inv,
+                     void* d_scal_L, void* d_scal_R, uint64_t* cross, void* stream) {
+#define CALL(P) return ipa_round_impl<P>(log_n, k, d_a, d_b, d_s, d_s_inv, u, u_inv, d_scal_L, d_scal_R, cross, (hipStream_t)stream)
+    ZK_DISPATCH_FR(curve, CALL);
+#undef CALL
+}
+
+int zk_ipa_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a, const uint64_t* b,
+                              void* d_out, void* stream) {
+#define CALL(P) return ipa_verify_scalars_impl<P>(log_n, u, u_inv, a, b, d_out, (hipStream_t)stream)
+    ZK_DISPATCH_FR(curve, CALL);
+#undef CALL
+}
+
+}  // extern "C"

@@ -1,0 +1,288 @@
+"""
+The Bulletproofs inner-product argument with the reference's interface and transcript
+(python/zksnake/subprotocol/bulletproofs/ipa.py:6-213): prove knowledge of a, b with commitment = <a, G> + <b, H> and
+<a, b> = the claimed product, in log2(n) rounds of two points each.
+
+The reference folds its generators every round (G' = u^-1 G_lo + u G_hi, about 2n two-scalar multiplications over a
+proof and new bases for every MSM).  Here G and H are NEVER folded: after k rounds the folded generator is
+G^(k)_j = sum_{i = j mod m} s_i G_i with the verifier's s vector, so every L_k, R_k is an MSM over the original G || H with
+scalars that one kernel writes (zk_ipa_round_dev, include/zkmi.h).  One MSM plan over the 2n fixed bases serves the
+commitment, every round and the verifier; a, b, s and the MSM scalars stay in HBM; per round only the challenge goes to
+the device and only the two cross products and L, R come back.
+
+Two differences from the reference, both deliberate:
+  * the generators come from this project's own `hash_to_curve` (transcript.py), so proofs are not interchangeable with
+    the reference's;
+  * when `Q` was given to the constructor, `verify` mirrors `prove`: it uses that Q and does not append the commitment.
+    The reference's verify always derives Q from the transcript and therefore rejects its own Q-given proofs.
+
+G1 only, both curves, n <= 2^21 (2n bases fit the largest split-scalar MSM plan).
+"""
+
+import ctypes
+import time
+
+import numpy as np
+
+from .. import _native as N
+from .._algebra import PointArray, _point_class
+from ..ecc import CurvePointSize, EllipticCurve
+from ..frvec import DevVec, FrOps
+from ..mle import sumcheck_round
+from ..transcript import FiatShamirTranscript, hash_to_curve, hash_to_curve_limbs
+from ..utils import next_power_of_two, split_list
+
+MAX_LOG = 21
+
+
+class InnerProductProof:
+
+    def __init__(self, a: int, b: int, L: list, R: list):
+        self.a = a
+        self.b = b
+        self.L = L
+        self.R = R
+
+    def to_bytes(self) -> bytes:
+        s = b""
+        for L, R in zip(self.L, self.R):
+            s += bytes(L.to_bytes())
+            s += bytes(R.to_bytes())
+        s += self.a.to_bytes(32, "little")
+        s += self.b.to_bytes(32, "little")
+        return bytes(s)
+
+    @classmethod
+    def from_bytes(cls, s: bytes, crv="BN254"):
+        E = EllipticCurve(crv)
+        n = CurvePointSize[crv].value
+        assert (len(s) - 64) % n == 0, "Invalid proof length"
+        field_s = split_list(s[-64:], 32)
+        s = split_list(s[:-64], n)
+        Ls, Rs = [], []
+        for i in range(0, len(s), 2):
+            Ls.append(E.from_hex(s[i].hex()))
+            Rs.append(E.from_hex(s[i + 1].hex()))
+        return InnerProductProof(int.from_bytes(field_s[0], "little"), int.from_bytes(field_s[1], "little"), Ls, Rs)
+
+
+class InnerProductArgument:
+    """InnerProductArgument(size, curve, seed=b"InnerProductProof", Q=None): vectors of next_power_of_two(size) elements.
+
+    `G`, `H` are PointArrays of n G1 points, hashed from `seed` (on the host, about a millisecond per point) unless
+    `generators=(G, H)` hands them in; they may be assigned (a PointArray or a list of n points), which drops the MSM plan and
+    the cached transcript bytes.  `prove(.., profile=True)` runs the two MSMs of a round one after the other instead of side
+    by side and leaves the per-round milliseconds in `last_profile` (tools/ipa_bench.py)."""
+
+    def __init__(self, size, curve, seed=b"InnerProductProof", Q=None, *, generators=None):
+        self.n = next_power_of_two(size)
+        self.log_n = self.n.bit_length() - 1
+        if self.log_n > MAX_LOG:
+            raise ValueError(f"the inner-product argument takes at most 2^{MAX_LOG} elements")
+        self.E = EllipticCurve(curve)
+        self._ops = FrOps(self.E.order)
+        self._bases = None
+        self._bytes = {}
+        self._hasher = None
+        if generators is not None:
+            self.G, self.H = generators
+        else:
+            self.G = PointArray(self.E.curve_id, 1, hash_to_curve_limbs(seed, b"G", curve, self.n))
+            self.H = PointArray(self.E.curve_id, 1, hash_to_curve_limbs(seed, b"H", curve, self.n))
+        self.Q = Q
+        self.last_profile = None
+
+    # -- generators --
+    def _as_array(self, points):
+        if not isinstance(points, PointArray):
+            points = list(points)
+            limbs = np.zeros((len(points), N.point_limbs(self.E.curve_id, 1)), dtype=np.uint64)
+            for i, pt in enumerate(points):
+                if not isinstance(pt, self.E.curve.PointG1):
+                    raise TypeError("generators are G1 points of the argument's curve")
+                limbs[i] = pt._limbs
+            points = PointArray(self.E.curve_id, 1, limbs)
+        if points.curve_id != self.E.curve_id or points.group != 1:
+            raise TypeError("generators are G1 points of the argument's curve")
+        if len(points) != self.n:
+            raise ValueError(f"{self.n} generators expected, got {len(points)}")
+        return points
+
+    def _set(self, name, points):
+        self.__dict__["_" + name] = self._as_array(points)
+        self._bytes.pop(name, None)
+        self._hasher = None
+        if self._bases is not None:
+            self._bases.release()
+            self._bases = None
+
+    G = property(lambda self: self._G, lambda self, v: self._set("G", v))
+    H = property(lambda self: self._H, lambda self, v: self._set("H", v))
+
+    def _generator_bytes(self, name):
+        """every point's compressed encoding, back to back: what appending the points one by one adds to the transcript"""
+        if name not in self._bytes:
+            self._bytes[name] = getattr(self, name).to_bytes()
+        return self._bytes[name]
+
+    def _plan(self, slot=0):
+        """the MSM plan over G || H (2n bases in HBM), created once per generator set; slot 1 is a clone over the same bases
+        with a workspace and a stream of its own, for the second MSM of a round"""
+        if self._bases is None:
+            self._bases = PointArray(self.E.curve_id, 1, np.concatenate([self._G.limbs, self._H.limbs]))
+        return self._bases.plan(slot=slot, concurrent=slot > 0)
+
+    def _msm(self, vec, timings=None):
+        """<vec, G || H> for a device vector of 2n scalars"""
+        lib = N.load()
+        out = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
+        N.check(lib.zk_msm_plan_run(self._plan(), 2 * self.n, vec.ptr(), 1, 0, 0, N.u64p(out), None))
+        if timings is not None:
+            ms = (ctypes.c_float * 5)()
+            lib.zk_msm_plan_timings(self._plan(), ms, 5)
+            timings.append(float(ms[4]))
+        return _point_class(self.E.curve_id, 1)._from_limbs(out)
+
+    def _msm_pair(self, vec_l, vec_r):
+        """<vec_l, G || H> and <vec_r, G || H> in flight together, each on its plan's stream"""
+        lib, out = N.load(), []
+        handles = [self._plan(0), self._plan(1)]
+        for h, vec in zip(handles, (vec_l, vec_r)):
+            N.check(lib.zk_msm_plan_enqueue(h, 2 * self.n, vec.ptr(), 1, 0, 0, N.STREAM_PLAN))
+        for h in handles:
+            limbs = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
+            N.check(lib.zk_msm_plan_finish(h, N.u64p(limbs)))
+            out.append(_point_class(self.E.curve_id, 1)._from_limbs(limbs))
+        return out
+
+    def _load(self, dst, offset, values):
+        """values (list of ints, limb array or DevVec; at most n elements) -> dst[offset : offset + n], zero padded"""
+        ops, n = self._ops, self.n
+        if isinstance(values, DevVec):
+            if values.n > n:
+                raise ValueError(f"at most {n} elements")
+            if values.n:
+                ops.d_copy(values.n, values.ptr(), dst.ptr(offset))
+            return
+        limbs = ops.limbs(values)
+        if limbs.shape[0] > n:
+            raise ValueError(f"at most {n} elements")
+        if limbs.shape[0]:
+            dst.upload(limbs, offset)
+            if isinstance(values, np.ndarray):
+                N.check(N.load().zk_vec_canon_dev(ops.cid, limbs.shape[0], dst.ptr(offset), None))
+
+    def _transcript(self, transcript):
+        """the caller's transcript, or the default one, with every G_i and then every H_i appended.  The default transcript
+        always starts with the same label and generators (64 MiB of them at n = 2^20), so its hasher is kept after the first
+        use and copied."""
+        if transcript is not None:
+            transcript.append(self._generator_bytes("G"))
+            transcript.append(self._generator_bytes("H"))
+            return transcript
+        transcript = FiatShamirTranscript(self.n.to_bytes(32, "big"), field=self.E.order)
+        if self._hasher is None:
+            transcript.append(self._generator_bytes("G"))
+            transcript.append(self._generator_bytes("H"))
+            self._hasher = transcript.hasher.copy()
+        else:
+            transcript.hasher = self._hasher.copy()
+        return transcript
+
+    def prove(self, a, b, transcript=None, profile=False):
+        """(InnerProductProof, commitment, <a, b>).  a, b: lists of ints, (k, 4) limb arrays or DevVecs of at most n elements
+        (zero padded); device vectors of the caller are not modified."""
+        N.ensure_gpu()
+        lib, ops, n, log_n, r = N.load(), self._ops, self.n, self.log_n, self.E.order
+        transcript = self._transcript(transcript)
+
+        ab_vec = DevVec(2 * n)                       # a || b: the commitment's scalars, then folded in place
+        self._load(ab_vec, 0, a)
+        self._load(ab_vec, n, b)
+        a_ptr, b_ptr = ab_vec.ptr(0), ab_vec.ptr(n)
+        ab = sum(sumcheck_round(ops, log_n, [a_ptr, b_ptr], [(1, (0, 1))])[:2 if log_n else 1]) % r
+        commitment = self._msm(ab_vec)
+        if self.Q is not None:
+            Q = self.Q
+        else:
+            transcript.append(commitment)
+            Q = hash_to_curve(transcript.get_challenge(), b"Q", self.E.name)
+
+        s, s_inv = DevVec(n, zero=False), DevVec(n, zero=False)
+        scal_l, scal_r = DevVec(2 * n, zero=False), DevVec(2 * n, zero=False)
+        cross = np.zeros((2, 4), dtype=np.uint64)
+        L_list, R_list, rounds = [], [], []
+        u = u_inv = None
+        for k in range(log_n + 1):
+            t0 = time.perf_counter()
+            last = k == log_n
+            N.check(lib.zk_ipa_round_dev(ops.cid, log_n, k, a_ptr, b_ptr, s.ptr(), s_inv.ptr(),
+                                         None if u is None else N.u64p(u), None if u is None else N.u64p(u_inv),
+                                         None if last else scal_l.ptr(), None if last else scal_r.ptr(),
+                                         None if last else N.u64p(cross), None))
+            if last:
+                break
+            t1 = time.perf_counter()
+            if profile:      # one after the other, so that each run's stage timings can be read
+                msm_ms = []
+                L = self._msm(scal_l, msm_ms)
+                R = self._msm(scal_r, msm_ms)
+            else:
+                L, R = self._msm_pair(scal_l, scal_r)
+            t2 = time.perf_counter()
+            c = ops.ints(cross)
+            L = L + Q * c[0]
+            R = R + Q * c[1]
+            L_list.append(L)
+            R_list.append(R)
+            transcript.append(L)
+            transcript.append(R)
+            challenge = transcript.get_challenge_scalar()
+            u, u_inv = ops.one(challenge), ops.one(pow(challenge, -1, r))
+            if profile:
+                t3 = time.perf_counter()
+                rounds.append({"round": k, "kernel_ms": (t1 - t0) * 1e3, "msm_wall_ms": (t2 - t1) * 1e3, "msm_ms": sum(msm_ms),
+                               "host_ms": (t3 - t2) * 1e3})
+        final = ops.ints(ab_vec.download(1, 0)) + ops.ints(ab_vec.download(1, n))
+        if profile:
+            self.last_profile = rounds
+        return InnerProductProof(final[0], final[1], L_list, R_list), commitment, ab
+
+    def verify(self, proof: InnerProductProof, commitment, inner_product_result, transcript=None):
+        assert len(proof.L) < 32, "Argument size is too big"
+        if len(proof.L) != self.log_n or len(proof.R) != self.log_n:
+            return False
+        N.ensure_gpu()
+        lib, ops, n, log_n, r = N.load(), self._ops, self.n, self.log_n, self.E.order
+        transcript = self._transcript(transcript)
+        if self.Q is not None:
+            Q = self.Q
+        else:
+            transcript.append(commitment)
+            Q = hash_to_curve(transcript.get_challenge(), b"Q", self.E.name)
+
+        us, sum_LR = [], self.E.curve.PointG1.identity()
+        for L, R in zip(proof.L, proof.R):
+            transcript.append(L)
+            transcript.append(R)
+            u = transcript.get_challenge_scalar()
+            us.append(u)
+            sum_LR = sum_LR + L * pow(u, 2, r) + R * pow(u, -2, r)
+
+        scal = DevVec(2 * n, zero=False)
+        u_l = ops.limbs(us) if us else None
+        ui_l = ops.limbs([pow(u, -1, r) for u in us]) if us else None
+        N.check(lib.zk_ipa_verify_scalars_dev(ops.cid, log_n, None if u_l is None else N.u64p(u_l), None if ui_l is None else N.u64p(ui_l),
+                                              N.u64p(ops.one(proof.a)), N.u64p(ops.one(proof.b)), scal.ptr(), None))
+        lhs = commitment + Q * (inner_product_result % r)
+        rhs = self._msm(scal) + Q * (proof.a * proof.b % r) - sum_LR
+        return lhs == rhs
+
+    def release(self):
+        """free the MSM plan over G || H (it is rebuilt on the next use)"""
+        if self._bases is not None:
+            self._bases.release()
+            self._bases = None
+
+
+__all__ = ["InnerProductArgument", "InnerProductProof"]

@@ -4,14 +4,89 @@ a challenge is the digest, and the digest also seeds the hasher that continues t
 
 Byte encodings are the reference's, quirks included: an int is written big-endian on `bit_length()` BYTES (so with
 leading zero bytes; 0 contributes nothing), a point as its compressed encoding, a list as the concatenation of its
-items.  (hash_to_scalar / hash_to_curve of transcript.py:6-25 belong to the Bulletproofs/IPA side of the reference,
-outside this backend's path.)
+items.
+
+`hash_to_curve` / `hash_to_scalar` have the reference's signatures (transcript.py:6-25) but NOT its bytes.  The reference
+takes its map from a Rust crate (bn254_hash2curve) whose source is not available to this project, so its output can be
+neither reproduced nor checked; the map below is this project's own.  GENERATORS THEREFORE DIFFER FROM THE REFERENCE'S, SO
+PROOFS BUILT ON THEM (the inner-product argument) ARE NOT INTERCHANGEABLE WITH IT; everything else is its protocol.
+
+The map is try-and-increment over
+    digest = sha512(b"zksnake-amd-h2c-v1" || len(dst) on 2 bytes BE || dst || len(data) on 8 bytes BE || data
+                    || index on 8 bytes BE || ctr on 4 bytes BE)
+with x = digest (big-endian) mod q; the first ctr = 0, 1, .. for which x^3 + b is a non-zero square is taken
+(q = 3 mod 4 on both curves, so the root is one power), and y is the smaller root.  On BLS12-381 the point is multiplied
+by 0xd201000000010001 into the subgroup of order r, and a counter that lands on the identity is skipped.  Point i of a
+`size`-long call uses index = i: there is no chaining (the reference hashes the previous point, transcript.py:22-23), so
+the points are independent of each other and of `size`.  `hash_to_scalar` is the digest of the same framing with
+index = ctr = 0, reduced mod r.  Not constant time: for public generators only.
 """
 
 import hashlib
 
-from .constant import BN254_SCALAR_FIELD
-from .ecc import ispointG1, ispointG2
+import numpy as np
+
+from . import _native as N
+from .constant import BLS12_381_MODULUS, BLS12_381_SCALAR_FIELD, BN254_MODULUS, BN254_SCALAR_FIELD
+from .ecc import EllipticCurve, ispointG1, ispointG2
+
+_H2C_TAG = b"zksnake-amd-h2c-v1"
+_BLS_G1_COFACTOR = 0xD201000000010001   # 1 - z: clears the cofactor of BLS12-381 G1
+
+
+def _h2c_prefix(data, domain_separation_tag):
+    if isinstance(data, str):
+        data = data.encode()
+    data, dst = bytes(data), bytes(domain_separation_tag)
+    return hashlib.sha512(_H2C_TAG + len(dst).to_bytes(2, "big") + dst + len(data).to_bytes(8, "big") + data)
+
+
+def hash_to_scalar(data: bytes, domain_separation_tag: bytes, curve: str = "BN254") -> int:
+    h = _h2c_prefix(data, domain_separation_tag)
+    h.update((0).to_bytes(8, "big") + (0).to_bytes(4, "big"))
+    return int.from_bytes(h.digest(), "big") % EllipticCurve(curve).order
+
+
+def hash_to_curve_limbs(data: bytes, domain_separation_tag: bytes, curve: str = "BN254", size: int = 1):
+    """the points of `hash_to_curve` as a (size, limbs) uint64 array of affine coordinates: what a PointArray holds"""
+    cid = N.curve_id(curve)
+    q, b = (BN254_MODULUS, 3) if cid == 0 else (BLS12_381_MODULUS, 4)
+    nb = 8 * N.fq_limbs(cid)
+    root_exp = (q + 1) // 4
+    prefix = _h2c_prefix(data, domain_separation_tag)
+    out = np.zeros((size, N.point_limbs(cid, 1)), dtype=np.uint64)
+    if cid == 1:
+        lib = N.load()
+        cof = N.ints_to_limbs([_BLS_G1_COFACTOR], 4)
+    for i in range(size):
+        at = prefix.copy()
+        at.update(i.to_bytes(8, "big"))
+        ctr = 0
+        while True:
+            h = at.copy()
+            h.update(ctr.to_bytes(4, "big"))
+            ctr += 1
+            x = int.from_bytes(h.digest(), "big") % q
+            rhs = (x * x * x + b) % q
+            y = pow(rhs, root_exp, q)         # the root when there is one: squaring it back is the test for a square
+            if rhs == 0 or y * y % q != rhs:
+                continue
+            y = min(y, q - y)
+            out[i] = np.frombuffer(x.to_bytes(nb, "little") + y.to_bytes(nb, "little"), dtype=np.uint64)
+            if cid == 1:
+                row = out[i].copy()
+                N.check(lib.zk_point_mul(cid, 1, N.u64p(row), N.u64p(cof), N.u64p(out[i])))
+                if not out[i].any():
+                    continue
+            break
+    return out
+
+
+def hash_to_curve(data: bytes, domain_separation_tag: bytes, curve: str = "BN254", size: int = 1):
+    """one G1 point (size = 1) or a list of `size` points; see the module docstring for the map"""
+    cls = EllipticCurve(curve).curve.PointG1
+    points = [cls._from_limbs(row.copy()) for row in hash_to_curve_limbs(data, domain_separation_tag, curve, size)]
+    return points[0] if size == 1 else points
 
 
 def _encode(item) -> bytes:
