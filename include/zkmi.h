@@ -468,6 +468,48 @@ int zk_ipa_round_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_
 int zk_ipa_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a, const uint64_t* b,
                               void* d_out, void* stream);
 
+/* ---- GKR over layered circuits, the sparse side (csrc/gkr.hip) ----------------------------------------------------------
+ * Layer j of a circuit has n_j wires and a dense table W_j of 2^k_j canonical Fr elements in device memory (zero beyond n_j),
+ * 1 <= k_j <= ZK_GKR_MAX_LOG.  Gate g of layer j is (types[g]: 0 ADD / 1 MUL, in1[g], in2[g]) with in1, in2 < n_(j-1): three
+ * device arrays (u8, u32, u32) in gate order.  THE CALLER has checked the indices (LayeredCircuit.compile does): the kernels
+ * gather W_(j-1)[in1[g]] without a bounds test.  The wiring predicates add_j, mul_j of gkr.py:113-171 have one non-zero entry
+ * per gate, at (a, b, c) = (g, in1[g], in2[g]); every entry point below sums over gates instead of over that hypercube.
+ * Scalars are canonical 4-limb integers in host memory, reduced on entry when >= r.  Sums are fixed-order (exact and
+ * repeatable); no atomics.  ZK_ERR_ARG for a null pointer, a size out of range or an output that overlaps another buffer of
+ * the call; nothing is written then. */
+#define ZK_GKR_MAX_LOG 24
+/* Rows of the two CSRs with more entries than this leave the lane-per-row kernel (spmv.py's LONG_ROW). */
+#define ZK_GKR_LONG_ROW 64
+/* d_out[g] = types[g] ? W[in1[g]] * W[in2[g]] : W[in1[g]] + W[in2[g]] for g < n_gates, 0 for n_gates <= g < 2^log_out: the table
+ * of layer j from the table d_w (2^log_prev elements) of layer j-1 (LayeredCircuit.evaluate, layered_circuit.py:77-104, one
+ * layer).  n_gates <= 2^log_out.  Enqueues only. */
+int zk_gkr_layer_eval_dev(int curve, uint64_t n_gates, const void* d_types, const void* d_in1, const void* d_in2, int log_prev,
+                          const void* d_w, int log_out, void* d_out, void* stream);
+/* d_out[x] = eq(r, x) = prod_{t<k} (bit t of x ? r[t] : 1 - r[t]) for x < 2^k; r: k * 4 limbs (NULL when k = 0, which gives [1]).
+ * Every element is k products from the challenges, which travel as kernel arguments.  Enqueues only. */
+int zk_gkr_eq_table_dev(int curve, int k, const uint64_t* r, void* d_out, void* stream);
+/* The two bookkeeping passes of the prover over a CSR of the layer's gates with 2^log_rows rows (log_rows = k_(j-1)):
+ * row_ptr (2^log_rows + 1, u32), and per entry gate (the gate's index a, u32), other (the gate's input that is not the row,
+ * u32) and types (u8); n_entries = the layer's gates <= 2^log_e.  d_e: E[a] = eq(r, a), 2^log_e elements (log_e = k_j).
+ *   phase 1, rows = in1, other = in2, d_w = W_(j-1):   P[b] = sum_ADD E[a] + sum_MUL E[a] W[c],   Q[b] = sum_ADD E[a] W[c]
+ *   phase 2, rows = in2, other = in1, d_e2 = eq(u, .): Aadd[c] = sum_ADD E[a] E2[b],              Amul[c] = sum_MUL E[a] E2[b]
+ * Both outputs (2^log_rows elements each) come from one pass with one product per gate; every row is written, empty rows as
+ * zero.  Rows of more than ZK_GKR_LONG_ROW entries: long_rows (n_long, u32), item_ptr (n_long + 1, u32) and items (n_items pairs
+ * [e0, e1) of u32) cut them into work items as spmv.py's long_row_items does; d_partials: 2 * n_items elements of scratch.
+ * With n_long = 0 these four may be NULL.  Enqueue only. */
+int zk_gkr_phase1_dev(int curve, int log_rows, uint64_t n_entries, const void* d_row_ptr, const void* d_gate, const void* d_other,
+                      const void* d_types, uint64_t n_long, const void* d_long_rows, const void* d_item_ptr, uint64_t n_items,
+                      const void* d_items, void* d_partials, int log_e, const void* d_e, const void* d_w, void* d_p, void* d_q, void* stream);
+int zk_gkr_phase2_dev(int curve, int log_rows, uint64_t n_entries, const void* d_row_ptr, const void* d_gate, const void* d_other,
+                      const void* d_types, uint64_t n_long, const void* d_long_rows, const void* d_item_ptr, uint64_t n_items,
+                      const void* d_items, void* d_partials, int log_e, const void* d_e, const void* d_e2, void* d_add, void* d_mul,
+                      void* stream);
+/* out[0..3] = add~_j(r, u, v) = sum over ADD gates of E_r[g] E_u[in1[g]] E_v[in2[g]], out[4..7] = the same over MUL gates (host,
+ * canonical): what gkr.py:262-263, :331-332 get from two dense selector polynomials.  d_er: eq(r, .), 2^log_a elements;
+ * d_eu, d_ev: eq(u, .), eq(v, .), 2^log_prev elements each.  n_gates <= 2^log_a.  Synchronises the stream. */
+int zk_gkr_wiring_eval_dev(int curve, uint64_t n_gates, const void* d_types, const void* d_in1, const void* d_in2, int log_a,
+                           const void* d_er, int log_prev, const void* d_eu, const void* d_ev, uint64_t* out, void* stream);
+
 /* Dense-polynomial helpers over Fr used by the PlonK prover (python/zksnake/plonk/protocol.py:157-484); canonical
  * coefficients, lowest degree first, host memory.  They replace Polynomial.__call__ (src/bn254/polynomial.rs:491-516),
  * Polynomial.__truediv__ by a linear factor (:404-438), the batch_modinv + accumulator loop of protocol.py:296-307 and

@@ -40,6 +40,8 @@ MSM_ROUTE_RANGED, MSM_ROUTE_ONE_LEVEL, MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO
 MSM_ROUTES_TWO_LEVEL = (MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL)
 IPA_MAX_LOG = 22  # ZK_IPA_MAX_LOG: an inner-product argument has at most 2^22 elements per vector
 MLE_TILE_LOG = 8  # ZK_MLE_TILE_LOG: variables one launch of the multilinear kernels folds per 256-element tile
+GKR_MAX_LOG = 24  # ZK_GKR_MAX_LOG: a layer of a GKR circuit has at most 2^24 wires
+GKR_LONG_ROW = 64  # ZK_GKR_LONG_ROW: CSR rows with more entries leave the lane-per-row kernel of the GKR passes
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -136,6 +138,11 @@ SIGNATURES = {
                                    ctypes.POINTER(_vp), _u64p, _vp]),
     "zk_ipa_round_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _u64p, _u64p, _vp, _vp, _u64p, _vp]),
     "zk_ipa_verify_scalars_dev": (_i, [_i, _i, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
+    "zk_gkr_layer_eval_dev": (_i, [_i, _u64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "zk_gkr_eq_table_dev": (_i, [_i, _i, _u64p, _vp, _vp]),
+    "zk_gkr_phase1_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "zk_gkr_phase2_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "zk_gkr_wiring_eval_dev": (_i, [_i, _u64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _u64p, _vp]),
     "zk_fr_poly_eval": (_i, [_i, _u64, _u64p, _u64p, _u64p]),
     "zk_fr_poly_div_linear": (_i, [_i, _u64, _u64p, _u64p, _u64p, _u64p]),
     "zk_fr_grand_product": (_i, [_i, _u64, _u64p, _u64p, _u64p]),

@@ -6,8 +6,9 @@ drawn between rounds and one more at the end.
 The prover's per-round work -- fix one variable of every table, then sum f(X, x') over the rest of the hypercube at four
 values of X -- is ONE pass on the GPU (zk_sumcheck_round_dev) for polynomials of the form
     f(x) = sum_t c_t * prod_j M_{t,j}(x),        at most 3 factors per term, 8 terms, 8 tables          (ProductPolynomial)
-which covers a plain multilinear polynomial (one table, one factor) and the GKR round polynomial
-add*(W_b + W_c) + mul*W_b*W_c as three terms over tables broadcast to the same variables.  The reference evaluates s at the
+which covers a plain multilinear polynomial (one table, one factor) and both phases of the GKR round polynomial
+add*(W_b + W_c) + mul*W_b*W_c as subprotocol/gkr.py builds them from per-gate sums (GkrPolynomial: tables of one layer's size;
+broadcasting add, mul, W_b, W_c to the same 2k variables works too but costs 2^(2k) elements per table).  The reference evaluates s at the
 four 4th roots of unity and runs an inverse FFT (sumcheck.py:49-58); here s(0), s(1), s(2), s(3) come back from the device
 and are interpolated with Python integers -- the same polynomial of degree <= 3, hence the same `coeffs()`.
 
@@ -163,8 +164,8 @@ class Sumcheck:
         """(sum_claim, [round polynomials], challenges) for any SumcheckPolynomial.  Pass the caller's `transcript` when this
         runs inside a larger protocol, so that the challenges depend on what came before."""
         assert poly.n == self.n
-        if isinstance(poly, ProductPolynomial):
-            sum_claim = poly.sum()     # the same number as below, without moving the table to the host
+        if callable(getattr(poly, "sum", None)):
+            sum_claim = poly.sum()     # the same number as below, without moving the table to the host (ProductPolynomial, GkrPolynomial)
         else:
             sum_claim = sum(poly.to_evaluations()) % self.order
         transcript = transcript or FiatShamirTranscript(b"sumcheck", field=self.order)
