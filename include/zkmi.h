@@ -467,6 +467,41 @@ int zk_ipa_round_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_
  * element.  log_n = 0 gives [a, b].  Enqueues only. */
 int zk_ipa_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a, const uint64_t* b,
                               void* d_out, void* stream);
+/* zk_ipa_round_dev with a weighted H side: at k = 0 with d_h_weight non-NULL (n canonical elements, read only, part of the
+ * overlap check) s_inv[i] = h_weight[i] instead of 1, so that every later round and the verifier's H scalars carry the weight:
+ * the argument then runs over H'_i = h_weight[i] H_i without H' ever being formed (a range proof passes y^-i).  For k >= 1
+ * d_h_weight must be NULL (ZK_ERR_ARG otherwise); with NULL this is zk_ipa_round_dev. */
+int zk_ipa_round_seeded_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const void* d_h_weight,
+                            const uint64_t* u, const uint64_t* u_inv, void* d_scal_L, void* d_scal_R, uint64_t* cross, void* stream);
+
+/* ---- Bulletproofs range proof, scalar side (csrc/rangeproof.hip) --------------------------------------------------------
+ * subprotocol/bulletproofs/range_proof.py for m values of n bits in one argument over N = n m positions (the reference has
+ * m = 1): n = 2^log_bits, N = 2^log_N, 0 <= log_bits <= 7, log_bits <= log_N <= ZK_IPA_MAX_LOG.  Position k = j n + i is bit i of
+ * value j.  d_values: m x 2 64-bit limbs in device memory, the low 128 bits of each value, low limb first; bits at or above n
+ * are ignored.  Vectors are canonical Fr elements in device memory; y, y_inv, z, x, a, b, u, u_inv are canonical 4-limb
+ * integers in host memory, reduced on entry when >= r.  With
+ *     a_L[k] = bit i of v_j,  a_R = a_L - 1,  l0 = a_L - z,  l1 = s_L,
+ *     r0[k] = y^k (a_R[k] + z) + z^(2+j) 2^i,  r1[k] = y^k s_R[k]
+ * the prover's entry points write the scalars of A, the coefficients of t(X) = <l0 + l1 X, r0 + r1 X>, and l, r at X = x.
+ * y^k, y_inv^k and z^(2+j) are built per thread from the squarings g^(2^t), t <= 18, which travel as kernel arguments, and step
+ * by g^(2^18) per grid-stride item; 2^i is the integer with bit i set.  Workgroups of 256 threads on a grid capped at 1024
+ * workgroups: a thread takes a second item first at N = 2^19.  ZK_ERR_ARG for a null pointer, sizes out of range, an unknown
+ * curve or an output that overlaps another buffer of the call; nothing is written then. */
+/* d_out (2N elements) = a_L || a_R: out[k] in {0, 1}, out[N+k] = a_L[k] ? 0 : r-1.  Enqueues only. */
+int zk_rp_bits_dev(int curve, int log_bits, int log_N, const void* d_values, void* d_out, void* stream);
+/* t_out (12 limbs, host) = t0 = <l0, r0>, t1 = <l0, r1> + <l1, r0>, t2 = <l1, r1>.  d_s = s_L || s_R, 2N elements, read only.
+ * One pass, three fixed-order sums (exact and repeatable); l0, r0 are not stored.  Synchronises the stream. */
+int zk_rp_poly_dev(int curve, int log_bits, int log_N, const void* d_values, const void* d_s, const uint64_t* y, const uint64_t* z,
+                   uint64_t* t_out, void* stream);
+/* d_ab[k] = l[k] = l0[k] + x l1[k], d_ab[N+k] = r[k] = r0[k] + x r1[k] (2N elements: the a || b of the inner-product argument),
+ * d_h_weight[k] = y_inv^k (N elements: the weights of zk_ipa_round_seeded_dev).  y * y_inv = 1 is not checked.  Enqueues only. */
+int zk_rp_eval_dev(int curve, int log_bits, int log_N, const void* d_values, const void* d_s, const uint64_t* y, const uint64_t* y_inv,
+                   const uint64_t* z, const uint64_t* x, void* d_ab, void* d_h_weight, void* stream);
+/* The verifier's scalars of G || H (range_proof.py:273-280) with s_k the s vector of the inner-product argument above:
+ * d_out[k] = -z - a s_k,  d_out[N+k] = z + y_inv^k (z^(2+j) 2^i - b s_k^-1), 2N elements.  u, u_inv: log_N * 4 limbs each (may
+ * be NULL when log_N = 0).  Enqueues only. */
+int zk_rp_verify_scalars_dev(int curve, int log_bits, int log_N, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a,
+                             const uint64_t* b, const uint64_t* y_inv, const uint64_t* z, void* d_out, void* stream);
 
 /* ---- GKR over layered circuits, the sparse side (csrc/gkr.hip) ----------------------------------------------------------
  * Layer j of a circuit has n_j wires and a dense table W_j of 2^k_j canonical Fr elements in device memory (zero beyond n_j),

@@ -138,6 +138,11 @@ SIGNATURES = {
                                    ctypes.POINTER(_vp), _u64p, _vp]),
     "zk_ipa_round_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _u64p, _u64p, _vp, _vp, _u64p, _vp]),
     "zk_ipa_verify_scalars_dev": (_i, [_i, _i, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
+    "zk_ipa_round_seeded_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _u64p, _u64p, _vp, _vp, _u64p, _vp]),
+    "zk_rp_bits_dev": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    "zk_rp_poly_dev": (_i, [_i, _i, _i, _vp, _vp, _u64p, _u64p, _u64p, _vp]),
+    "zk_rp_eval_dev": (_i, [_i, _i, _i, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _vp, _vp, _vp]),
+    "zk_rp_verify_scalars_dev": (_i, [_i, _i, _i, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
     "zk_gkr_layer_eval_dev": (_i, [_i, _u64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "zk_gkr_eq_table_dev": (_i, [_i, _i, _u64p, _vp, _vp]),
     "zk_gkr_phase1_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -46,19 +46,22 @@ __global__ __launch_bounds__(MLE_TILE) void ipa_fold_kernel(uint64_t m, IpaChall
     }
 }
 
-// i < n: s[i], s_inv[i] take the challenge of the round before (init: they become 1), and -- write != 0, m >= 2 live elements of
-// a, b -- the 2n scalars of L and of R are written, zeros included.  With j = i mod m, h = m / 2 the partner of j is j ^ h.
+// i < n: s[i], s_inv[i] take the challenge of the round before (init: they become 1, or s_inv[i] the caller's h_weight[i]), and --
+// write != 0, m >= 2 live elements of a, b -- the 2n scalars of L and of R are written, zeros included.  With j = i mod m,
+// h = m / 2 the partner of j is j ^ h.
 template <class P>
 __global__ __launch_bounds__(MLE_TILE) void ipa_scalars_kernel(uint64_t n, uint64_t m, int shift, int init, int write, IpaChallenge<P> c,
                                                                const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                                uint32_t* __restrict__ s, uint32_t* __restrict__ s_inv,
-                                                               uint32_t* __restrict__ scal_l, uint32_t* __restrict__ scal_r) {
+                                                               const uint32_t* __restrict__ h_weight, uint32_t* __restrict__ scal_l,
+                                                               uint32_t* __restrict__ scal_r) {
     const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
     const Fp<P> r2 = fp_const<P>(P::R2), zero = fp_zero<P>();
     for (uint64_t i = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; i < n; i += stride) {
         Fp<P> sv, si;
         if (init) {
             sv = si = fp_raw_one<P>();
+            if (h_weight) si = load_fr<P>(h_weight + i * P::W);
         } else {
             const bool bit = (i >> shift) & 1;
             sv = fp_reduce_full<P>(fp_mul<P>(load_fr<P>(s + i * P::W), bit ? c.u_m : c.ui_m));
@@ -124,17 +127,18 @@ static unsigned ipa_blocks(uint64_t items) {
 }
 
 template <class P>
-static int ipa_round_impl(int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const uint64_t* u, const uint64_t* u_inv,
-                          void* d_scal_l, void* d_scal_r, uint64_t* cross, hipStream_t st) {
+static int ipa_round_impl(int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const void* d_h_weight, const uint64_t* u,
+                          const uint64_t* u_inv, void* d_scal_l, void* d_scal_r, uint64_t* cross, hipStream_t st) {
     if (log_n < 0 || log_n > IPA_MAX_LOG || k < 0 || k > log_n) return fail(ZK_ERR_ARG, "ipa_round: need 0 <= k <= log_n <= 22");
     if (!d_a || !d_b || !d_s || !d_s_inv) return fail(ZK_ERR_ARG, "ipa_round: null vector");
     if (k == 0 ? (u || u_inv) : (!u || !u_inv)) return fail(ZK_ERR_ARG, "ipa_round: a challenge goes with every round but the first, and only those");
+    if (k && d_h_weight) return fail(ZK_ERR_ARG, "ipa_round: the weights of s_inv go with round 0 only");
     const bool write = k < log_n;
     if (write && (!d_scal_l || !d_scal_r || !cross)) return fail(ZK_ERR_ARG, "ipa_round: null output");
     const uint64_t eb = P::W * 4, n = 1ull << log_n, m = n >> k;
-    const void* buf[6] = {d_a, d_b, d_s, d_s_inv, write ? d_scal_l : nullptr, write ? d_scal_r : nullptr};
-    const uint64_t len[6] = {n * eb, n * eb, n * eb, n * eb, 2 * n * eb, 2 * n * eb};
-    for (int x = 0; x < 6; ++x)
+    const void* buf[7] = {d_a, d_b, d_s, d_s_inv, write ? d_scal_l : nullptr, write ? d_scal_r : nullptr, d_h_weight};
+    const uint64_t len[7] = {n * eb, n * eb, n * eb, n * eb, 2 * n * eb, 2 * n * eb, n * eb};
+    for (int x = 0; x < 7; ++x)
         for (int y = 0; y < x; ++y)
             if (buf[x] && buf[y] && ranges_overlap(buf[x], len[x], buf[y], len[y])) return fail(ZK_ERR_ARG, "ipa_round: two buffers overlap");
 
@@ -147,7 +151,8 @@ static int ipa_round_impl(int log_n, int k, void* d_a, void* d_b, void* d_s, voi
         ZK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(ipa_scalars_kernel<P>, dim3(ipa_blocks(n)), dim3(MLE_TILE), 0, st, n, m, log_n - k, k == 0 ? 1 : 0, write ? 1 : 0, c,
-                       (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_s, (uint32_t*)d_s_inv, (uint32_t*)d_scal_l, (uint32_t*)d_scal_r);
+                       (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_s, (uint32_t*)d_s_inv, (const uint32_t*)d_h_weight, (uint32_t*)d_scal_l,
+                       (uint32_t*)d_scal_r);
     ZK_HIP(hipGetLastError());
     if (!write) return ZK_OK;
 
@@ -192,7 +197,12 @@ extern "C" {
 
 int zk_ipa_round_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const uint64_t* u, const uint64_t* u_inv,
                      void* d_scal_L, void* d_scal_R, uint64_t* cross, void* stream) {
-#define CALL(P) return ipa_round_impl<P>(log_n, k, d_a, d_b, d_s, d_s_inv, u, u_inv, d_scal_L, d_scal_R, cross, (hipStream_t)stream)
+    return zk_ipa_round_seeded_dev(curve, log_n, k, d_a, d_b, d_s, d_s_inv, nullptr, u, u_inv, d_scal_L, d_scal_R, cross, stream);
+}
+
+int zk_ipa_round_seeded_dev(int curve, int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const void* d_h_weight,
+                            const uint64_t* u, const uint64_t* u_inv, void* d_scal_L, void* d_scal_R, uint64_t* cross, void* stream) {
+#define CALL(P) return ipa_round_impl<P>(log_n, k, d_a, d_b, d_s, d_s_inv, d_h_weight, u, u_inv, d_scal_L, d_scal_R, cross, (hipStream_t)stream)
     ZK_DISPATCH_FR(curve, CALL);
 #undef CALL
 }

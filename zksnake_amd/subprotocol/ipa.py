@@ -199,8 +199,7 @@ class InnerProductArgument:
         ab_vec = DevVec(2 * n)                       # a || b: the commitment's scalars, then folded in place
         self._load(ab_vec, 0, a)
         self._load(ab_vec, n, b)
-        a_ptr, b_ptr = ab_vec.ptr(0), ab_vec.ptr(n)
-        ab = sum(sumcheck_round(ops, log_n, [a_ptr, b_ptr], [(1, (0, 1))])[:2 if log_n else 1]) % r
+        ab = sum(sumcheck_round(ops, log_n, [ab_vec.ptr(0), ab_vec.ptr(n)], [(1, (0, 1))])[:2 if log_n else 1]) % r
         commitment = self._msm(ab_vec)
         if self.Q is not None:
             Q = self.Q
@@ -208,6 +207,16 @@ class InnerProductArgument:
             transcript.append(commitment)
             Q = hash_to_curve(transcript.get_challenge(), b"Q", self.E.name)
 
+        L_list, R_list, a_final, b_final = self._rounds(ab_vec, Q, transcript, profile=profile)
+        return InnerProductProof(a_final, b_final, L_list, R_list), commitment, ab
+
+    def _rounds(self, ab_vec, Q, transcript, h_weight=None, profile=False):
+        """The log2(n) rounds over the device vector a || b (2n elements, folded in place): (L list, R list, a, b).  Every L, R is
+        appended to `transcript`.  h_weight (a DevVec of n elements, or None) starts s_inv at h_weight[i] instead of 1, so that
+        the argument runs over H'_i = h_weight[i] H_i with the plan over the original H (zk_ipa_round_seeded_dev): a range
+        proof's y^-i.  A challenge of 0 has no inverse: ValueError."""
+        lib, ops, n, log_n, r = N.load(), self._ops, self.n, self.log_n, self.E.order
+        a_ptr, b_ptr = ab_vec.ptr(0), ab_vec.ptr(n)
         s, s_inv = DevVec(n, zero=False), DevVec(n, zero=False)
         scal_l, scal_r = DevVec(2 * n, zero=False), DevVec(2 * n, zero=False)
         cross = np.zeros((2, 4), dtype=np.uint64)
@@ -216,10 +225,11 @@ class InnerProductArgument:
         for k in range(log_n + 1):
             t0 = time.perf_counter()
             last = k == log_n
-            N.check(lib.zk_ipa_round_dev(ops.cid, log_n, k, a_ptr, b_ptr, s.ptr(), s_inv.ptr(),
-                                         None if u is None else N.u64p(u), None if u is None else N.u64p(u_inv),
-                                         None if last else scal_l.ptr(), None if last else scal_r.ptr(),
-                                         None if last else N.u64p(cross), None))
+            N.check(lib.zk_ipa_round_seeded_dev(ops.cid, log_n, k, a_ptr, b_ptr, s.ptr(), s_inv.ptr(),
+                                                h_weight.ptr() if h_weight is not None and k == 0 else None,
+                                                None if u is None else N.u64p(u), None if u is None else N.u64p(u_inv),
+                                                None if last else scal_l.ptr(), None if last else scal_r.ptr(),
+                                                None if last else N.u64p(cross), None))
             if last:
                 break
             t1 = time.perf_counter()
@@ -246,7 +256,7 @@ class InnerProductArgument:
         final = ops.ints(ab_vec.download(1, 0)) + ops.ints(ab_vec.download(1, n))
         if profile:
             self.last_profile = rounds
-        return InnerProductProof(final[0], final[1], L_list, R_list), commitment, ab
+        return L_list, R_list, final[0], final[1]
 
     def verify(self, proof: InnerProductProof, commitment, inner_product_result, transcript=None):
         assert len(proof.L) < 32, "Argument size is too big"
