@@ -1,5 +1,6 @@
-"""Helper of tests/test_gpu_stream_state.py: the stream primitives both sides use, and the scenarios that need a process of
-their own (a twiddle table known to hold 16 stages, a first call of a given kind, zk_shutdown).
+"""Helper of tests/test_gpu_stream_state.py and tests/test_gpu_stream_state_protocols.py: the stream primitives and the
+upload-behind-a-spin plumbing both use, and the scenarios that need a process of their own (a twiddle table known to hold 16
+stages, a first call of a given kind, zk_shutdown).
 
 Run as `python stream_state_child.py <scenario>`: prints ONE JSON line {"scenario", "checks": {name: bool}, "timing": {..}}.
 Every expectation is the CPU oracle (oracle/corc.py), compared with ==.  Not a test module: pytest does not collect it."""
@@ -7,6 +8,7 @@ Every expectation is the CPU oracle (oracle/corc.py), compared with ==.  Not a t
 import ctypes
 import json
 import os
+import random
 import sys
 import time
 
@@ -23,8 +25,8 @@ from zksnake_amd import _native as N  # noqa: E402
 from zksnake_amd.device import DeviceBuffer, PinnedArray  # noqa: E402
 
 CURVES = (("BN254", 0), ("BLS12_381", 1))
-# Spin requests (microseconds).  SPIN_US parks a stream in the scenarios that assert "still in flight"; measured on an MI355X
-# (EXPERIMENTS.md "Stream-state tests"): see the docstring of tests/test_gpu_stream_state.py for the two numbers behind it.
+# Spin requests (microseconds).  SPIN_US parks a stream in the scenarios that assert "still in flight"; what both last on an
+# MI355X, and the slowest step SPIN_US has to outlast, are in EXPERIMENTS.md "Stream-state tests".
 SPIN_US = 200_000
 SPIN_SHORT_US = 20_000   # upload-behind-a-spin cases: only has to outlast the host's enqueueing of one call
 
@@ -90,6 +92,60 @@ class Staged:
 
     def download(self):
         return self.dev.download(self.shape, self.dtype)
+
+
+# ---- inputs and plumbing of the upload-behind-a-spin tests (test_gpu_stream_state.py, test_gpu_stream_state_protocols.py) ----
+
+def vals(p, n, seed):
+    """n field elements with 0 and r-1 among them"""
+    rnd = random.Random(seed * 7919 + (p & 0xFFFF))
+    v = [rnd.randrange(p) for _ in range(n)]
+    if n > 2:
+        v[1], v[n - 1] = 0, p - 1
+    return v
+
+
+def L(ints):
+    return N.ints_to_limbs(ints, 4)
+
+
+def I(limbs):
+    return N.limbs_to_ints(np.ascontiguousarray(limbs).reshape(-1, 4))
+
+
+def one(v):
+    return N.u64p(N.ints_to_limbs([v], 4))
+
+
+def staged(stale, real):
+    return Staged(L(stale), L(real))
+
+
+def behind_spin(gpu, inputs, call, read=None):
+    """park a fresh stream, queue the uploads of the real inputs behind the spin, issue `call(stream)` on it, synchronise;
+    returns read() (or what call returned).  The uploads must have been queued while the spin was provably running."""
+    st = new_stream(gpu)
+    try:
+        d, t0 = parked(gpu, st, SPIN_SHORT_US)
+        for s in inputs:
+            s.send(gpu, st)
+        msg = in_flight(d, t0, time.perf_counter(), "queueing the uploads")
+        got = call(st)
+        sync(gpu, st)
+        assert msg is None, msg
+        return read() if read else got
+    finally:
+        N.check(gpu.zk_stream_destroy(st))
+
+
+def settle(got, on_real, on_stale):
+    assert on_real != on_stale, "the case does not distinguish the real input from the stale one"
+    assert got == on_real, "differs from the model on the uploaded input"
+    assert got != on_stale, "equals the model on the STALE device content: part of the call ran on another stream"
+
+
+def host4(k=1):
+    return np.full((k, 4), 0xA5A5A5A5, dtype=np.uint64)
 
 
 def ntt_dev(lib, cid, inverse, log_n, ptr, st):

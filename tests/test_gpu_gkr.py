@@ -2,9 +2,16 @@
 
 The model runs each layer's sumcheck on the four dense tables of 2^(2k) entries; the prover under test never builds them.
 Kernel tests call the C entry points themselves, with outputs pre-filled with garbage where "every row is written" is
-the claim."""
+the claim.
 
+The sizes at which a thread takes a SECOND item are derived from the constants they sit on (GKR_MAX_BLOCKS of csrc/gkr.hip, read
+from the source; MLE_TILE; ITEM of zksnake_amd/spmv.py) and the derivation is asserted: a changed constant fails there, then
+the tests move.  At those sizes E is a table of powers g^i made on the device and pinned at about 64 indices, and every
+expectation is one Python loop with a running power."""
+
+import os
 import random
+import re
 
 import numpy as np
 import pytest
@@ -27,8 +34,17 @@ from zksnake_amd.transcript import FiatShamirTranscript
 pytestmark = pytest.mark.gpu
 
 T = N.MLE_TILE_LOG
+TILE = 1 << T
 FIELDS = (("BN254", BN254_SCALAR_FIELD), ("BLS12_381", BLS12_381_SCALAR_FIELD))
 BY_FIELD = pytest.mark.parametrize("name,p", FIELDS, ids=[f[0] for f in FIELDS])
+with open(os.path.join(os.path.dirname(os.path.abspath(N.__file__)), "csrc", "gkr.hip")) as _f:
+    MAX_BLOCKS = int(re.search(r"constexpr unsigned GKR_MAX_BLOCKS = (\d+);", _f.read()).group(1))   # read from the source
+GRID = MAX_BLOCKS * TILE               # threads of a capped grid: item GRID is some thread's second
+EQ_SECOND_LOG = GRID.bit_length()      # the smallest k whose 2^k entries do not fit one sweep of the grid
+WIRING_SECOND = GRID + TILE + 1        # gates: the grid strides, and the workgroup of the last gate holds that gate alone
+LONG_SECOND = TILE * ITEM + 1          # entries of one row: TILE + 1 work items, so a thread of gkr_phase_long_kernel takes two
+assert (GRID, EQ_SECOND_LOG, WIRING_SECOND, LONG_SECOND) == (2**18, 19, 2**18 + 257, 256 * ITEM + 1)   # the sizes the tests were written for
+TOP_SIZE = 2 * TILE + 1                # "every term at the top of the range": two workgroups and one element
 
 
 def upload(ops, values):
@@ -82,6 +98,32 @@ def test_eq_table(gpu, name, p, k):
         out = garbage(1 << k, k)
         N.check(gpu.zk_gkr_eq_table_dev(ops.cid, k, N.u64p(raw), out.ptr(), None))
         assert ints(out, 1 << k) == G.eq_table(points[0], p)
+
+
+def eq_table_by_doubling(r, p):
+    """variable t doubles the table: the upper half is the lower half times r_t, and the lower half loses what the upper half got --
+    one product per entry of the result"""
+    tab = [1]
+    for rt in r:
+        hi = [e * rt % p for e in tab]
+        tab = [(e - h) % p for e, h in zip(tab, hi)] + hi
+    return tab
+
+
+@BY_FIELD
+def test_eq_table_where_a_thread_takes_a_second_item(gpu, name, p):
+    k = EQ_SECOND_LOG
+    ops = FrOps(p)
+    rnd = random.Random(f"eq {name}")
+    special = [rnd.randrange(p) for _ in range(k)]
+    special[2], special[T + 1], special[k - 1] = 0, 1, p - 1       # among them the variable that is bit 18: the second item's
+    for r in ([rnd.randrange(p) for _ in range(k)], special):
+        out = garbage(1 << k, k)
+        N.check(gpu.zk_gkr_eq_table_dev(ops.cid, k, N.u64p(N.ints_to_limbs(r, 4)), out.ptr(), None))
+        assert np.array_equal(out.download(), N.ints_to_limbs(eq_table_by_doubling(r, p), 4))
+        total = np.zeros(4, dtype=np.uint64)
+        N.check(gpu.zk_mle_sum_dev(ops.cid, 1 << k, out.ptr(), N.u64p(total), None))
+        assert N.limbs_to_ints(total.reshape(1, 4)) == [1]
 
 
 # ---- layer evaluation ----
@@ -170,6 +212,154 @@ def test_bookkeeping_passes_and_wiring(gpu, name, p, shape):
         assert ints(got, 1 << kp) == expect, label
     assert wiring_eval(ops, layer, r, u, v) == G.wiring(gates, r, u, v, p)
     assert (ints(w_vec, 1 << kp), ints(e_vec, 1 << k), ints(e2_vec, 1 << kp)) == (w, e, e2), "an input table was modified"
+
+
+def pin_indices(n, edges, seed):
+    """about 64 indices: first, last, workgroup edges, both sides of every edge in `edges`, random ones"""
+    fixed = {0, 1, n - 2, n - 1, TILE - 1, TILE, TILE + 1, 2 * TILE - 1, 2 * TILE, n - TILE - 1, n - TILE}
+    for e in edges:
+        fixed |= {e - 1, e, e + 1}
+    fixed = {i for i in fixed if 0 <= i < n}
+    rnd = random.Random(seed)
+    while len(fixed) < 64:
+        fixed.add(rnd.randrange(n))
+    return sorted(fixed)
+
+
+def powers_table(ops, g, n, edges):
+    """g^i for i < n, made on the device (zk_vec_powers_dev) and pinned against pow() before anyone uses it"""
+    vec = ops.d_powers(g, n)
+    for i in pin_indices(n, edges, n):
+        assert N.limbs_to_ints(vec.download(1, i)) == [pow(g, i, ops.r)], f"the table of powers, index {i}"
+    return vec
+
+
+def random_gates(seed, n, n_prev):
+    """(types, in1, in2) as numpy arrays, mixed types, wires 0 and n_prev - 1 among the inputs"""
+    rng = np.random.default_rng(seed)
+    types = rng.integers(0, 2, size=n, dtype=np.uint8)
+    in1, in2 = rng.integers(0, n_prev, size=n, dtype=np.uint32), rng.integers(0, n_prev, size=n, dtype=np.uint32)
+    in1[::7], in2[::5] = 0, n_prev - 1
+    return types, in1, in2
+
+
+def _wiring(gpu, ops, n, d_gates, k, er, kp, eu, ev):
+    out = np.full((2, 4), 0x77, dtype=np.uint64)
+    N.check(gpu.zk_gkr_wiring_eval_dev(ops.cid, n, *d_gates, k, er, kp, eu, ev, N.u64p(out), None))
+    return tuple(N.limbs_to_ints(out))
+
+
+@BY_FIELD
+def test_wiring_where_a_thread_takes_a_second_item(gpu, name, p):
+    """2^18 + 257 gates: gkr_wiring_kernel runs its capped grid of 1024 workgroups, 257 threads take a second gate, and
+    mle_combine_kernel reads 1024 partial pairs.  The kernel takes any field elements for its three tables: E_r = g^i."""
+    n, n_prev = WIRING_SECOND, 300
+    assert -(-n // TILE) > MAX_BLOCKS and n - GRID == TILE + 1
+    ops = FrOps(p)
+    k, kp = G.num_vars(n), G.num_vars(n_prev)
+    assert (k, kp) == (EQ_SECOND_LOG, 9)
+    rnd = random.Random(f"wiring {name}")
+    g = rnd.randrange(1 << 250, p)
+    types, in1, in2 = random_gates(18, n, n_prev)
+    d_gates = [DeviceBuffer.from_numpy(a) for a in (types, in1, in2)]
+    eu, ev = table(rnd, n_prev, kp, p), table(rnd, n_prev, kp, p)
+    er_vec = powers_table(ops, g, 1 << k, (GRID, n))
+    eu_vec, ev_vec = upload(ops, eu), upload(ops, ev)
+    got = _wiring(gpu, ops, n, [d.ptr for d in d_gates], k, er_vec.ptr(), kp, eu_vec.ptr(), ev_vec.ptr())
+    acc, power = [0, 0], 1
+    for t, b, c in zip(types.tolist(), in1.tolist(), in2.tolist()):
+        acc[t] += power * eu[b] * ev[c]
+        power = power * g % p
+    assert got == (acc[0] % p, acc[1] % p)
+    assert (ints(eu_vec, 1 << kp), ints(ev_vec, 1 << kp)) == (eu, ev), "an input table was modified"
+
+
+@BY_FIELD
+def test_phases_where_a_thread_of_the_long_rows_kernel_takes_a_second_item(gpu, name, p):
+    """one row of 256 ITEM + 1 entries in both CSRs (every gate reads wire 0 twice): 257 work items, the smallest count at which
+    gkr_phase_long_kernel strides.  With one row, each output is one sum over the gates: E = g^a, so one running power."""
+    n, n_prev = LONG_SECOND, 8
+    ops = FrOps(p)
+    rng = np.random.default_rng(21)
+    types = rng.integers(0, 2, size=n, dtype=np.uint8)
+    zeros = np.zeros(n, dtype=np.uint32)
+    layer = CompiledLayer(n_prev, types, zeros, zeros)
+    k, kp = layer.k, layer.k_prev
+    assert (k, kp) == (21, 3)
+    for csr in (layer.by_b, layer.by_c):
+        assert csr.n_long == 1 and csr.n_items == TILE + 1 == 257
+        assert csr.items.tolist()[-2:] == [[(TILE - 1) * ITEM, TILE * ITEM], [TILE * ITEM, n]]
+    rnd = random.Random(f"long {name}")
+    g = rnd.randrange(1 << 250, p)
+    w, e2 = table(rnd, n_prev, kp, p), table(rnd, n_prev, kp, p)
+    w[0], e2[0] = rnd.randrange(1, p), p - 1           # the one entry of each that is read
+    e_vec = powers_table(ops, g, 1 << k, (GRID, ITEM, TILE * ITEM, n))
+    w_vec, e2_vec = upload(ops, w), upload(ops, e2)
+    out = [garbage(1 << kp, s) for s in range(4)]
+    N.check(gpu.zk_gkr_phase1_dev(ops.cid, *layer.by_b.args(), k, e_vec.ptr(), w_vec.ptr(), out[0].ptr(), out[1].ptr(), None))
+    N.check(gpu.zk_gkr_phase2_dev(ops.cid, *layer.by_c.args(), k, e_vec.ptr(), e2_vec.ptr(), out[2].ptr(), out[3].ptr(), None))
+    sums, power = [0, 0], 1
+    for t in types.tolist():
+        sums[t] += power
+        power = power * g % p
+    s_add, s_mul = sums[0] % p, sums[1] % p
+    want = ((s_add + s_mul * w[0]) % p, s_add * w[0] % p, s_add * e2[0] % p, s_mul * e2[0] % p)
+    for got, expect, label in zip(out, want, ("P", "Q", "Aadd", "Amul")):
+        assert ints(got, 1 << kp) == [expect] + [0] * 7, label
+    assert (ints(w_vec, 1 << kp), ints(e2_vec, 1 << kp)) == (w, e2), "an input table was modified"
+
+
+@pytest.mark.parametrize("log_rows", [3, T + 1], ids=["8 rows", "two workgroups of rows"])
+@BY_FIELD
+def test_empty_layers_through_the_c_abi(gpu, name, p, log_rows):
+    """no gate at all: an all-zero row_ptr and null gate arrays.  Every row is written as zero over garbage, and the wiring
+    predicates are (0, 0)"""
+    ops = FrOps(p)
+    rnd = random.Random(31)
+    n_rows = 1 << log_rows
+    row_ptr = DeviceBuffer.from_numpy(np.zeros(n_rows + 1, dtype=np.uint32))
+    e_vec, y_vec = upload(ops, table(rnd, 2, 1, p)), upload(ops, table(rnd, n_rows, log_rows, p))
+    csr = (log_rows, 0, row_ptr.ptr, None, None, None, 0, None, None, 0, None, None)
+    for fn in (gpu.zk_gkr_phase1_dev, gpu.zk_gkr_phase2_dev):
+        out = [garbage(n_rows, s) for s in (7, 8)]
+        N.check(fn(ops.cid, *csr, 1, e_vec.ptr(), y_vec.ptr(), out[0].ptr(), out[1].ptr(), None))
+        assert not out[0].download().any() and not out[1].download().any()
+    assert _wiring(gpu, ops, 0, (None, None, None), 1, e_vec.ptr(), log_rows, y_vec.ptr(), y_vec.ptr()) == (0, 0)
+
+
+@BY_FIELD
+def test_sums_with_every_term_at_the_top_of_the_range(gpu, name, p):
+    """every entry of E, W, E2, E_r, E_u, E_v is p - 1, over 2 x 256 + 1 gates: wire 0 feeds 256 + 192 of them (a long row whose one
+    item ends in a short sweep), wire 1 feeds LONG_ROW (the longest lane-per-row sum), wire 2 feeds one.  The wiring kernel runs
+    three workgroups, the last with one gate, and its combine reads three partial pairs.  Every term is +-1, so each result is
+    also a count of gates."""
+    ops = FrOps(p)
+    n, n_prev = TOP_SIZE, 8
+    assert n == 513 and n - LONG_ROW - 1 > LONG_ROW
+    types = np.random.default_rng(41).integers(0, 2, size=n, dtype=np.uint8)
+    wire = np.array([0] * (n - LONG_ROW - 1) + [1] * LONG_ROW + [2], dtype=np.uint32)
+    gates = list(zip(types.tolist(), wire.tolist(), wire.tolist()))
+    layer = CompiledLayer(n_prev, types, wire, wire)
+    k, kp = layer.k, layer.k_prev
+    assert (k, kp) == (10, 3) and layer.by_b.n_long == layer.by_c.n_long == 1 and layer.by_b.n_items == 1
+    e, y = [p - 1] * (1 << k), [p - 1] * (1 << kp)
+    e_vec, y_vec = upload(ops, e), upload(ops, y)
+    out = [garbage(1 << kp, s) for s in range(4)]
+    N.check(gpu.zk_gkr_phase1_dev(ops.cid, *layer.by_b.args(), k, e_vec.ptr(), y_vec.ptr(), out[0].ptr(), out[1].ptr(), None))
+    N.check(gpu.zk_gkr_phase2_dev(ops.cid, *layer.by_c.args(), k, e_vec.ptr(), y_vec.ptr(), out[2].ptr(), out[3].ptr(), None))
+    got = [ints(o, 1 << kp) for o in out]
+    assert got == list(G.phase1_tables(gates, kp, y, e, p)) + list(G.phase2_tables(gates, kp, e, y, p))
+    n_mul = [int(types[wire == b].sum()) for b in range(n_prev)]
+    n_add = [int((wire == b).sum()) - m for b, m in enumerate(n_mul)]
+    # E W = E E2 = 1 and E = -1: P = -#ADD + #MUL, Q = #ADD, Aadd = #ADD, Amul = #MUL, row by row
+    assert got == [[(m - a) % p for a, m in zip(n_add, n_mul)], n_add, n_add, n_mul]
+    d_gates = (layer.d_types.ptr, layer.d_in1.ptr, layer.d_in2.ptr)
+    wired = _wiring(gpu, ops, n, d_gates, k, e_vec.ptr(), kp, y_vec.ptr(), y_vec.ptr())
+    model = [0, 0]
+    for a, (t, b, c) in enumerate(gates):
+        model[t] = (model[t] + e[a] * y[b] * y[c]) % p
+    assert wired == tuple(model) == ((-sum(n_add)) % p, (-sum(n_mul)) % p)
+    assert (ints(e_vec, 1 << k), ints(y_vec, 1 << kp)) == (e, y), "an input table was modified"
 
 
 # ---- end to end ----

@@ -162,6 +162,31 @@ def test_fold_and_cross_where_a_thread_takes_a_second_item(gpu, name, p):
     assert cross == (sum(x * y for x, y in zip(a[:q4], b[q4:h])) % p, sum(x * y for x, y in zip(a[q4:h], b[:q4])) % p)
 
 
+@pytest.mark.parametrize("log_n", [3, 10])
+@pytest.mark.parametrize("name,p", FIELDS, ids=IDS)
+def test_cross_products_with_every_term_at_the_top_of_the_range(gpu, name, p, log_n):
+    """a = b = r - 1 everywhere and u = u^-1 = r - 1, through k = 0, 1, 2.  The vectors of this entry point are powers of two long,
+    so no size is "two workgroups and one element"; two sizes stand in for it.  At log_n = 10 the first cross products run two
+    full workgroups and the combine reads two of the 256 partial pairs it can take; from then on, and at log_n = 3 from the
+    start, a workgroup sums with most of its lanes idle.  Every product is +-1 times a power of two, so the cross products are
+    also counts: (n 2^k) / 2 in round k."""
+    ops, n = FrOps(p), 1 << log_n
+    a, b = [p - 1] * n, [p - 1] * n
+    s, s_inv = [None] * n, [None] * n
+    d_a, d_b = upload(a), upload(b)
+    d_s, d_si = poisoned(gpu, n), poisoned(gpu, n)
+    for k in range(3):
+        u = None if k == 0 else p - 1
+        want = M.round_step(log_n, k, a, b, s, s_inv, u, u, p)
+        d_l, d_r = poisoned(gpu, 2 * n), poisoned(gpu, 2 * n)
+        st, cross = call_round(gpu, ops, log_n, k, d_a, d_b, d_s, d_si, u, d_l, d_r, p)
+        N.check(st)
+        assert cross == want[2], f"round {k}"
+        assert cross == (((n << k) >> 1) % p,) * 2, f"round {k}: the count"
+        assert ints(d_l) == want[0] and ints(d_r) == want[1], f"the scalars of round {k}"
+        assert ints(d_a) == a and ints(d_b) == b and ints(d_s) == s and ints(d_si) == s_inv, f"the vectors after round {k}"
+
+
 @pytest.mark.parametrize("log_n", (0,) + SIZES + (SECOND_ITEM_LOG,))
 @pytest.mark.parametrize("name,p", FIELDS, ids=IDS)
 def test_verify_scalars(gpu, name, p, log_n):

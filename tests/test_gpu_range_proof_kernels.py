@@ -168,6 +168,21 @@ def test_poly_where_a_thread_takes_a_second_item(gpu, name, p):
     assert call_poly(gpu, FrOps(p).cid, lb, ln, d_values, d_s, y, z) == M.poly_contract(lb, ln, values, s, y, z, p)
 
 
+@pytest.mark.parametrize("log_bits,log_N", [(3, 3), (3, 9)])
+@pytest.mark.parametrize("name,p", FIELDS, ids=IDS)
+def test_poly_with_every_term_at_the_top_of_the_range(gpu, name, p, log_bits, log_N):
+    """every bit set, s_L = s_R = r - 1 everywhere, y = z = r - 1.  N is a power of two, so no size is "two workgroups and one
+    element"; two sizes stand in for it: 512 positions (two full workgroups, and the combine reads two of the 256 partial triples
+    it can take) and 8 (a workgroup that sums with 248 idle lanes).  With y = z = -1: l0 = 2, l1 = -1, r0[k] = -(-1)^k + (-1)^j 2^i,
+    r1[k] = -(-1)^k, and over an even N the alternating sums vanish: t0 = 2 S, t1 = -S, t2 = 0 with S = (2^n - 1) (m mod 2)."""
+    n, m = 1 << log_bits, 1 << (log_N - log_bits)
+    values, s = [MASK128] * m, [p - 1] * (2 << log_N)
+    got = call_poly(gpu, FrOps(p).cid, log_bits, log_N, upload_values(values), upload(s), p - 1, p - 1)
+    assert got == M.poly_contract(log_bits, log_N, values, s, p - 1, p - 1, p)
+    total = ((1 << n) - 1) * (m % 2)
+    assert (n * m) % 2 == 0 and got == (2 * total % p, -total % p, 0)
+
+
 # ---- zk_rp_eval_dev ------------------------------------------------------------------------------------------------------------
 def call_eval(gpu, cid, lb, ln, d_values, d_s, y, y_inv, z, x, d_ab, d_w):
     return gpu.zk_rp_eval_dev(cid, lb, ln, d_values.ptr(), d_s.ptr(), one(y), one(y_inv), one(z), one(x), d_ab.ptr(), d_w.ptr(), None)

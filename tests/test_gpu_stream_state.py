@@ -9,7 +9,8 @@ integer models of tests/, compared with ==.
 
 "In flight" is asserted: parked() measures the spin alone (D); wherever another stream (or the host) works while a stream is
 parked, the host time from queueing the spin to the end of that work must stay below D.
-  Spin request 200 ms (stream_state_child.SPIN_US).  Measured on an MI355X: NOT MEASURED YET (see EXPERIMENTS.md).
+  Spin requests 200 ms and 20 ms (stream_state_child.SPIN_US, SPIN_SHORT_US); D for both on an MI355X is in EXPERIMENTS.md,
+  "Stream-state tests".
 
 Sizes: 2^12 = first size with scratch (two passes), 2^16 = largest on the initial 16-stage table (a QAP there needs stage
 17), 2^17 = first growth for a plain transform and first three-pass plan (two scratch vectors).  Nothing is larger."""
@@ -28,6 +29,7 @@ import pytest
 import mle_model as M
 import stream_state_child as S
 from oracle import corc
+from stream_state_child import I, L, behind_spin, host4, one, settle, staged, vals
 from zksnake_amd import _native as N
 from zksnake_amd.constant import BLS12_381_SCALAR_FIELD, BN254_SCALAR_FIELD
 from zksnake_amd.device import DeviceBuffer
@@ -43,31 +45,6 @@ _REF = {}
 
 # ---- inputs and plumbing ------------------------------------------------------------------------------------------------
 
-def vals(p, n, seed):
-    """n field elements with 0 and r-1 among them"""
-    rnd = random.Random(seed * 7919 + (p & 0xFFFF))
-    v = [rnd.randrange(p) for _ in range(n)]
-    if n > 2:
-        v[1], v[n - 1] = 0, p - 1
-    return v
-
-
-def L(ints):
-    return N.ints_to_limbs(ints, 4)
-
-
-def I(limbs):
-    return N.limbs_to_ints(np.ascontiguousarray(limbs).reshape(-1, 4))
-
-
-def one(v):
-    return N.u64p(N.ints_to_limbs([v], 4))
-
-
-def staged(stale, real):
-    return S.Staged(L(stale), L(real))
-
-
 def ref_ntt(cid, log_n, seed, inverse=False):
     """(input limbs, oracle output): computed once, shared, never modified"""
     key = ("ntt", cid, log_n, seed, inverse)
@@ -82,33 +59,6 @@ def ref_qap(cid, log_n, seed):
     if key not in _REF:
         _REF[key] = S.qap_inputs(cid, log_n, 5000 + 100 * log_n + 10 * seed + cid)
     return _REF[key]
-
-
-def behind_spin(gpu, inputs, call, read=None):
-    """park a fresh stream, queue the uploads of the real inputs behind the spin, issue `call(stream)` on it, synchronise;
-    returns read() (or what call returned).  The uploads must have been queued while the spin was provably running."""
-    st = S.new_stream(gpu)
-    try:
-        d, t0 = S.parked(gpu, st, S.SPIN_SHORT_US)
-        for s in inputs:
-            s.send(gpu, st)
-        msg = S.in_flight(d, t0, time.perf_counter(), "queueing the uploads")
-        got = call(st)
-        S.sync(gpu, st)
-        assert msg is None, msg
-        return read() if read else got
-    finally:
-        N.check(gpu.zk_stream_destroy(st))
-
-
-def settle(got, on_real, on_stale):
-    assert on_real != on_stale, "the case does not distinguish the real input from the stale one"
-    assert got == on_real, "differs from the model on the uploaded input"
-    assert got != on_stale, "equals the model on the STALE device content: part of the call ran on another stream"
-
-
-def host4(k=1):
-    return np.full((k, 4), 0xA5A5A5A5, dtype=np.uint64)
 
 
 # ---- A.1: upload behind a spin, then compute ---------------------------------------------------------------------------
