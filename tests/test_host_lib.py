@@ -245,6 +245,42 @@ def test_dev_buf_gives_every_block_back_exactly_once(tmp_path):
     assert res.returncode == 0 and res.stdout.count(": ok") == 7 and "all ok" in res.stdout, res.stdout + res.stderr
 
 
+def test_protocol_host_sides_refuse_bad_arguments_under_sanitizers(tmp_path):
+    """the host side of csrc/ipa.hip and csrc/rangeproof.hip (argument rules, overlap checks, the conversion of the challenges,
+    the shared pieces of fr_sum.hip.h and ipa_chain.hip.h) as two stand-alone programs under the address and undefined-behaviour
+    sanitizers (tests/native/ipa_args_check.cpp, rangeproof_args_check.cpp, built by the recipe in their headers): a host-only
+    compile, an EMPTY offload bundle for the __hip_fatbin_<hash> symbol the object refers to, link, run.  The sanitizer runtimes
+    are linked into the programs.  A program sees no device on any machine, so the calls that pass the checks fail in the
+    launch with ZK_ERR_HIP, which is what it expects."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    magic = ",".join(f"'{c}'" for c in "__CLANG_OFFLOAD_BUNDLE__")
+    # on a machine with a GPU driver the HSA runtime starts up even with every device hidden and leaves 144 bytes of its own
+    # behind at exit; the leak check stays on for everything else
+    supp = tmp_path / "lsan.supp"
+    supp.write_text("leak:libhsa-runtime64\n")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", LSAN_OPTIONS=f"suppressions={supp}:print_suppressions=0")
+    for name in ("ipa_args_check", "rangeproof_args_check"):
+        obj, stub, exe = str(tmp_path / f"{name}.o"), str(tmp_path / f"{name}_stub"), str(tmp_path / name)
+        subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-mbmi2", "-madx",
+                               "-DZK_NOINLINE_MUL", *san, "-c", os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", obj], timeout=600)
+        undefined = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout
+        syms = sorted(set(re.findall(r"__hip_fatbin_[0-9a-f]+", undefined)))
+        assert syms, "the host-only object names no device image"
+        with open(stub + ".cpp", "w") as f:   # the magic string and a bundle count of zero: registered at load time, never looked into
+            f.write("#include <stdint.h>\nstruct bundle { char magic[24]; uint64_t count; };\n")
+            for sym in syms:
+                f.write(f'extern "C" __attribute__((aligned(4096))) const bundle {sym} = {{{{{magic}}}, 0}};\n')
+        subprocess.check_call(["g++", "-O0", "-c", stub + ".cpp", "-o", stub + ".o"], timeout=600)
+        subprocess.check_call([hipcc, "--offload-host-only", *san, "-o", exe, obj, stub + ".o"], timeout=600)
+        res = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0 and f"{name}: all ok" in res.stdout, res.stdout + res.stderr
+
+
 def test_build_script_falls_back_to_plain_hipcc_when_the_pass_pipeline_cannot_be_reproduced(tmp_path):
     """csrc/hipcc_noreassoc.sh drives clang / opt / llc by hand to leave LLVM's `reassociate` pass out of the device pipeline; on a
     toolchain whose O3 pipeline text has no such pass it must not fail the build (round-3 advisor finding) but compile the unit

@@ -127,4 +127,16 @@ inline int log2_u64(uint64_t n) {
     return l;
 }
 
+// ---- argument checks: byte spans of the caller's buffers ------------------------------------------------------
+inline bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+// the written span w against the first n of the spans (p[i], len[i]); an absent (null) or empty span is skipped
+inline bool overlaps_any(const void* w, uint64_t w_bytes, const void* const* p, const uint64_t* len, int n) {
+    for (int i = 0; i < n; ++i)
+        if (p[i] && len[i] && ranges_overlap(w, w_bytes, p[i], len[i])) return true;
+    return false;
+}
+
 }  // namespace zkmi

@@ -72,6 +72,14 @@ ZK_HD Fp<P> fp_one() {
     return fp_const<P>(P::ONE);
 }
 
+// the integer 1 (not Montgomery form): the canonical one in memory, and mont(x R, 1) = x
+template <class P>
+ZK_HD Fp<P> fp_raw_one() {
+    Fp<P> o = fp_zero<P>();
+    o.v[0] = 1;
+    return o;
+}
+
 // zero mod p: the representative is 0 or p
 template <class P>
 ZK_HD bool fp_is_zero(const Fp<P>& a) {
@@ -536,9 +544,7 @@ ZK_HD Fp<P> fp_from_canonical(const uint32_t* w) {
 // Montgomery form -> canonical integer in [0, p) as W words
 template <class P>
 ZK_HD void fp_to_canonical(uint32_t* w, const Fp<P>& a) {
-    Fp<P> o = fp_zero<P>();
-    o.v[0] = 1;
-    fp_pack<P>(w, fp_reduce_full<P>(fp_mul<P>(a, o)));
+    fp_pack<P>(w, fp_reduce_full<P>(fp_mul<P>(a, fp_raw_one<P>())));
 }
 
 // storage of Montgomery-form values (semi-reduced, < 2p < 2^(32 W)) in HBM / host buffers

@@ -1,7 +1,9 @@
-// fr_sum.hip.h -- exact, repeatable sums of Fr elements over a grid of any size: every workgroup of MLE_TILE threads adds its
-// values in a fixed tree and stores one canonical partial sum, and ONE workgroup adds the partial sums (mle_combine_kernel).
-// Shared by mle.hip and ipa.hip, with the tile constants both are launched with.
+// fr_sum.hip.h -- what the protocol kernels over Fr (mle.hip, ipa.hip, rangeproof.hip, gkr.hip, plonk.hip) share: the tile they
+// are launched with, the capped strided grid, host scalars into kernel arguments, and exact, repeatable sums over a grid of any
+// size: every workgroup of MLE_TILE threads adds its values in a fixed tree and stores one canonical partial sum, and ONE
+// workgroup adds the partial sums (mle_combine_kernel; FrSum is the host side of that).
 #pragma once
+#include <algorithm>
 #include "common.hip.h"
 #include "fr_mem.hip.h"
 
@@ -9,7 +11,24 @@ namespace zkmi {
 
 constexpr int MLE_TILE_LOG = ZK_MLE_TILE_LOG;
 constexpr int MLE_TILE = 1 << MLE_TILE_LOG;   // elements per tile == threads per workgroup
-static_assert(MLE_TILE == 256, "the kernels of mle.hip and ipa.hip are launched with 256 threads");
+static_assert(MLE_TILE == 256, "the kernels over Fr are launched with 256 threads");
+
+// the cap of every strided grid: 2^18 threads, so a pass over more items strides; also the most partial sums ONE workgroup adds
+constexpr unsigned FR_MAX_BLOCKS = 1024;
+static inline unsigned fr_blocks(uint64_t items) {
+    return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + MLE_TILE - 1) / MLE_TILE, 1), FR_MAX_BLOCKS);
+}
+
+// a host scalar (4 x 64-bit limbs, any value) as a kernel argument: x R, below 2r -- mont(d, x R) = x d
+template <class P>
+static Fp<P> fr_mont(const uint64_t* x) {
+    return fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(x));
+}
+// x mod r as an integer, below 2r: the start of a chain of products by Montgomery-form factors
+template <class P>
+static Fp<P> fr_canon(const uint64_t* x) {
+    return fp_mul<P>(fr_mont<P>(x), fp_raw_one<P>());
+}
 
 template <class P>
 __device__ __forceinline__ void lds_put(uint32_t (*lds)[MLE_TILE], int i, const Fp<P>& a) {
@@ -48,9 +67,30 @@ __global__ __launch_bounds__(MLE_TILE) void mle_combine_kernel(uint32_t count, i
     }
 }
 
-static inline bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
-}
+// The host side of a two-level sum of k values: alloc(), then the caller launches its own kernel on `blocks` workgroups, each of
+// which stores k partial sums at part() + blockIdx.x * k (block_sum_store), then finish().
+template <class P>
+struct FrSum {
+    mem::DevBuf buf;   // blocks x k partial sums | the k results
+    unsigned blocks = 0;
+    int k = 0;
+
+    int alloc(unsigned blocks_, int k_) {
+        blocks = blocks_;
+        k = k_;
+        return buf.alloc((size_t)(blocks + 1) * k * P::W * 4);
+    }
+    uint32_t* part() const { return buf.as(); }
+    // the combine behind the caller's kernel, ONE error check for both launches, the k results to `out` on the host; returns
+    // after the stream has run, so the block may go back to the allocator
+    int finish(uint64_t* out, hipStream_t st) const {
+        uint32_t* res = part() + (size_t)blocks * k * P::W;
+        hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, k, part(), res);
+        ZK_HIP(hipGetLastError());
+        ZK_HIP(hipMemcpyAsync(out, res, (size_t)k * P::W * 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        return ZK_OK;
+    }
+};
 
 }  // namespace zkmi

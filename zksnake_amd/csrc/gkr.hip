@@ -16,17 +16,15 @@
 //
 // Like mle.hip the kernels multiply canonical data directly: mont(x, y) = x y / R, so a sum of single products is closed with
 // R^2 and a sum of double products with R^3, once per thread, before the fixed-order workgroup sums of fr_sum.hip.h.
-// Workgroups of MLE_TILE threads.
-#include <algorithm>
-#include "common.hip.h"
-#include "fr_mem.hip.h"
+// Workgroups of MLE_TILE threads; the strided grids are capped at FR_MAX_BLOCKS (2^18 threads: item 2^18 is a second stride).
 #include "fr_sum.hip.h"
 
 namespace zkmi {
-using mem::DevBuf;
 
 constexpr int GKR_MAX_LOG = ZK_GKR_MAX_LOG;
-constexpr unsigned GKR_MAX_BLOCKS = 1024;   // the cap of the strided grids (mle.hip's): 2^18 threads, item 2^18 is a second stride
+// the cap under the name tests/test_gpu_gkr.py reads from this file to place its sizes; the launches use FR_MAX_BLOCKS
+constexpr unsigned GKR_MAX_BLOCKS = 1024;
+static_assert(GKR_MAX_BLOCKS == FR_MAX_BLOCKS, "the sizes of tests/test_gpu_gkr.py sit on the shared cap");
 constexpr uint32_t GKR_LONG_ROW = ZK_GKR_LONG_ROW;
 
 // ---- layer evaluation ------------------------------------------------------------------------------------------------
@@ -53,19 +51,11 @@ struct EqArgs {
     Fp<P> r_m[GKR_MAX_LOG], nr_m[GKR_MAX_LOG];  // r_t R and (1 - r_t) R
 };
 
-// the integer 1 (not Montgomery form): the canonical one, and the start of a chain of products by Montgomery-form factors
-template <class P>
-ZK_HD Fp<P> gkr_raw_one() {
-    Fp<P> o = fp_zero<P>();
-    o.v[0] = 1;
-    return o;
-}
-
 template <class P>
 __global__ __launch_bounds__(MLE_TILE) void gkr_eq_table_kernel(uint64_t n, int k, EqArgs<P> a, uint32_t* __restrict__ out) {
     const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
     for (uint64_t x = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; x < n; x += stride) {
-        Fp<P> v = gkr_raw_one<P>();
+        Fp<P> v = fp_raw_one<P>();   // the integer 1: the start of a chain of products by Montgomery-form factors
         for (int t = 0; t < k; ++t) v = fp_mul<P>(v, (x >> t) & 1 ? a.r_m[t] : a.nr_m[t]);
         store_fr<P>(out + x * P::W, fp_reduce_full<P>(v));
     }
@@ -198,10 +188,6 @@ __global__ __launch_bounds__(MLE_TILE) void gkr_wiring_kernel(uint64_t n_gates, 
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-static unsigned gkr_blocks(uint64_t items) {
-    return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + MLE_TILE - 1) / MLE_TILE, 1), GKR_MAX_BLOCKS);
-}
-
 static bool gkr_log_ok(int log_n) { return log_n >= 0 && log_n <= GKR_MAX_LOG; }
 
 template <class P>
@@ -215,7 +201,7 @@ static int gkr_layer_eval_impl(uint64_t n_gates, const void* types, const void* 
     if (n_gates && (ranges_overlap(out, eb << log_out, types, n_gates) || ranges_overlap(out, eb << log_out, in1, 4 * n_gates) ||
                     ranges_overlap(out, eb << log_out, in2, 4 * n_gates)))
         return fail(ZK_ERR_ARG, "gkr_layer_eval: d_out overlaps the gates");
-    hipLaunchKernelGGL(gkr_layer_eval_kernel<P>, dim3(gkr_blocks(n_out)), dim3(MLE_TILE), 0, st, n_gates, n_out, (const uint8_t*)types,
+    hipLaunchKernelGGL(gkr_layer_eval_kernel<P>, dim3(fr_blocks(n_out)), dim3(MLE_TILE), 0, st, n_gates, n_out, (const uint8_t*)types,
                        (const uint32_t*)in1, (const uint32_t*)in2, (const uint32_t*)w, (uint32_t*)out);
     ZK_HIP(hipGetLastError());
     return ZK_OK;
@@ -230,12 +216,12 @@ static int gkr_eq_table_impl(int k, const uint64_t* r, void* out, hipStream_t st
     for (int t = 0; t < GKR_MAX_LOG; ++t) {
         a.r_m[t] = a.nr_m[t] = fp_zero<P>();
         if (t < k) {
-            a.r_m[t] = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(r + 4 * t));
+            a.r_m[t] = fr_mont<P>(r + 4 * t);
             a.nr_m[t] = fp_sub<P>(one_m, a.r_m[t]);
         }
     }
     const uint64_t n = 1ull << k;
-    hipLaunchKernelGGL(gkr_eq_table_kernel<P>, dim3(gkr_blocks(n)), dim3(MLE_TILE), 0, st, n, k, a, (uint32_t*)out);
+    hipLaunchKernelGGL(gkr_eq_table_kernel<P>, dim3(fr_blocks(n)), dim3(MLE_TILE), 0, st, n, k, a, (uint32_t*)out);
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
@@ -265,10 +251,8 @@ static int gkr_phase_impl(const GkrCsr& c, int log_e, const void* tab_e, const v
     const uint64_t out_len[3] = {eb * n_rows, eb * n_rows, 2 * eb * c.n_items};
     for (int x = 0; x < 3; ++x) {
         if (!outs[x]) continue;
-        for (int y = 0; y < 9; ++y)
-            if (ins[y] && in_len[y] && ranges_overlap(outs[x], out_len[x], ins[y], in_len[y])) return fail(ZK_ERR_ARG, "gkr_phase: an output overlaps an input");
-        for (int y = 0; y < x; ++y)
-            if (ranges_overlap(outs[x], out_len[x], outs[y], out_len[y])) return fail(ZK_ERR_ARG, "gkr_phase: two outputs overlap");
+        if (overlaps_any(outs[x], out_len[x], ins, in_len, 9)) return fail(ZK_ERR_ARG, "gkr_phase: an output overlaps an input");
+        if (overlaps_any(outs[x], out_len[x], outs, out_len, x)) return fail(ZK_ERR_ARG, "gkr_phase: two outputs overlap");
     }
     hipLaunchKernelGGL((gkr_phase_rows_kernel<P, PHASE>), dim3((unsigned)((n_rows + MLE_TILE - 1) / MLE_TILE)), dim3(MLE_TILE), 0, st, n_rows,
                        (const uint32_t*)c.row_ptr, (const uint32_t*)c.gate, (const uint32_t*)c.other, (const uint8_t*)c.types,
@@ -290,18 +274,11 @@ static int gkr_wiring_eval_impl(uint64_t n_gates, const void* types, const void*
     if (!gkr_log_ok(log_a) || !gkr_log_ok(log_prev)) return fail(ZK_ERR_ARG, "gkr_wiring_eval: a layer has at most 2^24 wires");
     if (n_gates > (1ull << log_a)) return fail(ZK_ERR_ARG, "gkr_wiring_eval: more gates than the layer's table holds");
     if (!er || !eu || !ev || !out || (n_gates && (!types || !in1 || !in2))) return fail(ZK_ERR_ARG, "gkr_wiring_eval: null argument");
-    const size_t eb = P::W * 4;
-    const unsigned blocks = gkr_blocks(n_gates);
-    DevBuf part_buf;   // blocks x 2 partial sums | the 2 results
-    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * 2 * eb));
-    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * 2 * P::W;
-    hipLaunchKernelGGL(gkr_wiring_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, n_gates, (const uint8_t*)types, (const uint32_t*)in1,
-                       (const uint32_t*)in2, (const uint32_t*)er, (const uint32_t*)eu, (const uint32_t*)ev, part);
-    hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 2, part, res);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(out, res, 2 * eb, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    FrSum<P> sum;
+    ZK_HIP_RC(sum.alloc(fr_blocks(n_gates), 2));   // no gate: one workgroup, which stores two zeros
+    hipLaunchKernelGGL(gkr_wiring_kernel<P>, dim3(sum.blocks), dim3(MLE_TILE), 0, st, n_gates, (const uint8_t*)types, (const uint32_t*)in1,
+                       (const uint32_t*)in2, (const uint32_t*)er, (const uint32_t*)eu, (const uint32_t*)ev, sum.part());
+    return sum.finish(out, st);
 }
 
 }  // namespace zkmi

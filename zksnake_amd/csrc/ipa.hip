@@ -8,30 +8,18 @@
 //
 // Like mle.hip the kernels multiply canonical data by scalars carried in Montgomery form (mont(x, s R) = x s), so no
 // vector is ever converted; a product of two canonical values is closed with R^2.  Workgroups of MLE_TILE threads, the
-// grid capped at IPA_MAX_BLOCKS workgroups; the cross products are per-workgroup partial sums added by one workgroup.
-#include <algorithm>
-#include "common.hip.h"
-#include "fr_mem.hip.h"
-#include "fr_sum.hip.h"
+// grid capped at FR_MAX_BLOCKS workgroups (2^18 threads, so a pass over 2^19 items strides); the cross products are per-workgroup
+// partial sums added by one workgroup (fr_sum.hip.h).
+#include "ipa_chain.hip.h"
 
 namespace zkmi {
-using mem::DevBuf;
 
 constexpr int IPA_MAX_LOG = ZK_IPA_MAX_LOG;
-constexpr unsigned IPA_MAX_BLOCKS = 1024;   // the grid's cap (mle.hip's): 2^18 threads, so a pass over 2^19 items strides
 
 template <class P>
 struct IpaChallenge {
     Fp<P> u_m, ui_m;  // u R and u^-1 R
 };
-
-// the integer 1 (not Montgomery form): the canonical one in memory, and mont(x R, 1) = x
-template <class P>
-ZK_HD Fp<P> fp_raw_one() {
-    Fp<P> o = fp_zero<P>();
-    o.v[0] = 1;
-    return o;
-}
 
 // in place, j < m: a[j] = u a[j] + u^-1 a[j+m], b[j] = u^-1 b[j] + u b[j+m].  Element j is read and written by one thread only,
 // element j+m only read.
@@ -100,8 +88,8 @@ __global__ __launch_bounds__(MLE_TILE) void ipa_cross_kernel(uint64_t h, const u
 
 template <class P>
 struct IpaVerifyArgs {
-    Fp<P> u_m[IPA_MAX_LOG], ui_m[IPA_MAX_LOG];  // u_t R, u_t^-1 R
-    Fp<P> a, b;                                 // the proof's scalars, below 2r
+    IpaChain<P> c;
+    Fp<P> a, b;   // the proof's scalars, below 2r
 };
 
 // out[i] = a s_i, out[n+i] = b s_i^-1: log_n products each, the chain starting at the canonical a (b)
@@ -110,10 +98,11 @@ __global__ __launch_bounds__(MLE_TILE) void ipa_verify_scalars_kernel(uint64_t n
     const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
     for (uint64_t i = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; i < n; i += stride) {
         Fp<P> sa = v.a, sb = v.b;
+        // ipa_chain_run's loop, written out: through the call the BN254 instance comes out 4 VALU instructions longer (572 for 568)
         for (int t = 0; t < log_n; ++t) {
             const bool bit = (i >> (log_n - 1 - t)) & 1;
-            sa = fp_mul<P>(sa, bit ? v.u_m[t] : v.ui_m[t]);
-            sb = fp_mul<P>(sb, bit ? v.ui_m[t] : v.u_m[t]);
+            sa = fp_mul<P>(sa, bit ? v.c.u_m[t] : v.c.ui_m[t]);
+            sb = fp_mul<P>(sb, bit ? v.c.ui_m[t] : v.c.u_m[t]);
         }
         store_fr<P>(out + i * P::W, fp_reduce_full<P>(sa));
         store_fr<P>(out + (n + i) * P::W, fp_reduce_full<P>(sb));
@@ -121,10 +110,6 @@ __global__ __launch_bounds__(MLE_TILE) void ipa_verify_scalars_kernel(uint64_t n
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-
-static unsigned ipa_blocks(uint64_t items) {
-    return (unsigned)std::min<uint64_t>((items + MLE_TILE - 1) / MLE_TILE, IPA_MAX_BLOCKS);
-}
 
 template <class P>
 static int ipa_round_impl(int log_n, int k, void* d_a, void* d_b, void* d_s, void* d_s_inv, const void* d_h_weight, const uint64_t* u,
@@ -138,35 +123,28 @@ static int ipa_round_impl(int log_n, int k, void* d_a, void* d_b, void* d_s, voi
     const uint64_t eb = P::W * 4, n = 1ull << log_n, m = n >> k;
     const void* buf[7] = {d_a, d_b, d_s, d_s_inv, write ? d_scal_l : nullptr, write ? d_scal_r : nullptr, d_h_weight};
     const uint64_t len[7] = {n * eb, n * eb, n * eb, n * eb, 2 * n * eb, 2 * n * eb, n * eb};
-    for (int x = 0; x < 7; ++x)
-        for (int y = 0; y < x; ++y)
-            if (buf[x] && buf[y] && ranges_overlap(buf[x], len[x], buf[y], len[y])) return fail(ZK_ERR_ARG, "ipa_round: two buffers overlap");
+    for (int x = 1; x < 7; ++x)   // every buffer against the ones before it
+        if (buf[x] && overlaps_any(buf[x], len[x], buf, len, x)) return fail(ZK_ERR_ARG, "ipa_round: two buffers overlap");
 
     IpaChallenge<P> c;
     c.u_m = c.ui_m = fp_zero<P>();
     if (k) {
-        c.u_m = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u));
-        c.ui_m = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u_inv));
-        hipLaunchKernelGGL(ipa_fold_kernel<P>, dim3(ipa_blocks(m)), dim3(MLE_TILE), 0, st, m, c, (uint32_t*)d_a, (uint32_t*)d_b);
+        c.u_m = fr_mont<P>(u);
+        c.ui_m = fr_mont<P>(u_inv);
+        hipLaunchKernelGGL(ipa_fold_kernel<P>, dim3(fr_blocks(m)), dim3(MLE_TILE), 0, st, m, c, (uint32_t*)d_a, (uint32_t*)d_b);
         ZK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ipa_scalars_kernel<P>, dim3(ipa_blocks(n)), dim3(MLE_TILE), 0, st, n, m, log_n - k, k == 0 ? 1 : 0, write ? 1 : 0, c,
+    hipLaunchKernelGGL(ipa_scalars_kernel<P>, dim3(fr_blocks(n)), dim3(MLE_TILE), 0, st, n, m, log_n - k, k == 0 ? 1 : 0, write ? 1 : 0, c,
                        (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_s, (uint32_t*)d_s_inv, (const uint32_t*)d_h_weight, (uint32_t*)d_scal_l,
                        (uint32_t*)d_scal_r);
     ZK_HIP(hipGetLastError());
     if (!write) return ZK_OK;
 
     const uint64_t h = m >> 1;
-    const unsigned blocks = ipa_blocks(h);
-    DevBuf part_buf;   // blocks x 2 partial sums | the 2 results
-    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * 2 * eb));
-    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * 2 * P::W;
-    hipLaunchKernelGGL(ipa_cross_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, h, (const uint32_t*)d_a, (const uint32_t*)d_b, part);
-    hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 2, part, res);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(cross, res, 2 * eb, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    FrSum<P> sum;
+    ZK_HIP_RC(sum.alloc(fr_blocks(h), 2));
+    hipLaunchKernelGGL(ipa_cross_kernel<P>, dim3(sum.blocks), dim3(MLE_TILE), 0, st, h, (const uint32_t*)d_a, (const uint32_t*)d_b, sum.part());
+    return sum.finish(cross, st);
 }
 
 template <class P>
@@ -175,16 +153,11 @@ static int ipa_verify_scalars_impl(int log_n, const uint64_t* u, const uint64_t*
     if (log_n < 0 || log_n > IPA_MAX_LOG) return fail(ZK_ERR_ARG, "ipa_verify_scalars: need 0 <= log_n <= 22");
     if (!a || !b || !d_out || (log_n && (!u || !u_inv))) return fail(ZK_ERR_ARG, "ipa_verify_scalars: null argument");
     IpaVerifyArgs<P> v;
-    const Fp<P> one = fp_raw_one<P>();
-    for (int t = 0; t < IPA_MAX_LOG; ++t) {
-        v.u_m[t] = t < log_n ? fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u + 4 * t)) : fp_zero<P>();
-        v.ui_m[t] = t < log_n ? fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(u_inv + 4 * t)) : fp_zero<P>();
-    }
-    // mont(x R, 1) = x mod r, below 2r: the start of a chain of products
-    v.a = fp_mul<P>(fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(a)), one);
-    v.b = fp_mul<P>(fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(b)), one);
+    v.c = ipa_chain_fill<P>(log_n, u, u_inv);
+    v.a = fr_canon<P>(a);   // the start of a chain of products
+    v.b = fr_canon<P>(b);
     const uint64_t n = 1ull << log_n;
-    hipLaunchKernelGGL(ipa_verify_scalars_kernel<P>, dim3(ipa_blocks(n)), dim3(MLE_TILE), 0, st, n, log_n, v, (uint32_t*)d_out);
+    hipLaunchKernelGGL(ipa_verify_scalars_kernel<P>, dim3(fr_blocks(n)), dim3(MLE_TILE), 0, st, n, log_n, v, (uint32_t*)d_out);
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }

@@ -14,16 +14,16 @@
 // variables there, so fixing k variables reads the table once per MLE_TILE_LOG variables instead of k times.
 #include <algorithm>
 #include <vector>
-#include "common.hip.h"
-#include "fr_mem.hip.h"
 #include "fr_sum.hip.h"
 
 namespace zkmi {
 using mem::DevBuf;
 
-// MLE_TILE_LOG and MLE_TILE (elements per tile == threads per workgroup) come from fr_sum.hip.h
+// MLE_TILE_LOG and MLE_TILE (elements per tile == threads per workgroup), the grid's cap and the two-level sums come from fr_sum.hip.h
 constexpr int MLE_MAX_LOG = 40;
-constexpr unsigned MLE_MAX_PARTIALS = 1024;   // workgroups of a reduction; their partial sums are added by ONE workgroup
+// the cap under the name tests/test_gpu_fr_large.py reads from this file to place its sizes; the launches use FR_MAX_BLOCKS
+constexpr unsigned MLE_MAX_PARTIALS = 1024;
+static_assert(MLE_MAX_PARTIALS == FR_MAX_BLOCKS, "the sizes of tests/test_gpu_fr_large.py sit on the shared cap");
 constexpr int SC_MAX_TABLES = 8, SC_MAX_TERMS = 8, SC_MAX_DEG = 3;
 
 // ---- fix_variables ---------------------------------------------------------------------------------------
@@ -193,7 +193,7 @@ static int fix_chain(int log_n, const uint32_t* in, int k, const uint64_t* r, ui
         const int f = std::min(MLE_TILE_LOG, k - done);
         FixArgs<P> a;
         for (int s = 0; s < MLE_TILE_LOG; ++s)
-            a.r_m[s] = s < f ? fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(r + 4 * (done + s))) : fp_zero<P>();
+            a.r_m[s] = s < f ? fr_mont<P>(r + 4 * (done + s)) : fp_zero<P>();
         uint32_t* dst = done + f == k ? out : tmp[pass & 1];
         const uint64_t n = 1ull << cur_log;
         hipLaunchKernelGGL(mle_fix_kernel<P>, dim3((unsigned)((n + MLE_TILE - 1) / MLE_TILE)), dim3(MLE_TILE), 0, st, n, f, a, cur, dst);
@@ -242,17 +242,10 @@ static int mle_sum_impl(uint64_t n, const void* x, uint64_t* out, hipStream_t st
     if (n > (1ull << MLE_MAX_LOG)) return fail(ZK_ERR_ARG, "mle_sum: at most 2^40 elements");
     for (int k = 0; k < 4; ++k) out[k] = 0;
     if (n == 0) return ZK_OK;
-    const size_t eb = P::W * 4;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((n + MLE_TILE - 1) / MLE_TILE, MLE_MAX_PARTIALS);
-    DevBuf part_buf;   // blocks partial sums | the result
-    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * eb));
-    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * P::W;
-    hipLaunchKernelGGL(mle_sum_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, n, (const uint32_t*)x, part);
-    hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 1, part, res);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(out, res, eb, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    FrSum<P> sum;
+    ZK_HIP_RC(sum.alloc(fr_blocks(n), 1));
+    hipLaunchKernelGGL(mle_sum_kernel<P>, dim3(sum.blocks), dim3(MLE_TILE), 0, st, n, (const uint32_t*)x, sum.part());
+    return sum.finish(out, st);
 }
 
 template <class P>
@@ -310,7 +303,7 @@ static int sumcheck_round_impl(int log_n, int n_tables, const void* const* table
     a.n_tables = n_tables;
     a.n_terms = n_terms;
     a.fused = r ? 1 : 0;
-    a.r_m = r ? fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(r)) : fp_zero<P>();
+    a.r_m = r ? fr_mont<P>(r) : fp_zero<P>();
     for (int tb = 0; tb < SC_MAX_TABLES; ++tb) {
         a.in[tb] = nullptr;
         a.out[tb] = nullptr;
@@ -320,15 +313,13 @@ static int sumcheck_round_impl(int log_n, int n_tables, const void* const* table
         a.in[tb] = (const uint32_t*)tables[tb];
         a.out[tb] = r ? (uint32_t*)tables_out[tb] : nullptr;
     }
-    if (r)
-        for (int i = 0; i < n_tables; ++i) {
-            for (int j = 0; j < n_tables; ++j)
-                if (ranges_overlap(tables_out[i], eb << (log_n - 1), tables[j], eb << log_n))
-                    return fail(ZK_ERR_ARG, "sumcheck_round: a folded table overlaps an input table");
-            for (int j = 0; j < i; ++j)
-                if (ranges_overlap(tables_out[i], eb << (log_n - 1), tables_out[j], eb << (log_n - 1)))
-                    return fail(ZK_ERR_ARG, "sumcheck_round: two folded tables overlap");
-        }
+    uint64_t in_len[SC_MAX_TABLES], out_len[SC_MAX_TABLES];
+    std::fill_n(in_len, SC_MAX_TABLES, eb << log_n);
+    std::fill_n(out_len, SC_MAX_TABLES, (eb << log_n) / 2);
+    for (int i = 0; r && i < n_tables; ++i) {   // a folded table against every input and every folded table before it
+        if (overlaps_any(tables_out[i], out_len[i], tables, in_len, n_tables)) return fail(ZK_ERR_ARG, "sumcheck_round: a folded table overlaps an input table");
+        if (overlaps_any(tables_out[i], out_len[i], tables_out, out_len, i)) return fail(ZK_ERR_ARG, "sumcheck_round: two folded tables overlap");
+    }
     for (int t = 0; t < SC_MAX_TERMS; ++t) {
         a.deg[t] = 0;
         a.coeff_m[t] = fp_zero<P>();
@@ -349,16 +340,10 @@ static int sumcheck_round_impl(int log_n, int n_tables, const void* const* table
     const int vars = log_n - (r ? 1 : 0);           // variables of the tables s(.) is taken over
     const int single = vars == 0;
     const uint64_t pairs = single ? 1 : 1ull << (vars - 1);
-    const unsigned blocks = (unsigned)std::min<uint64_t>((pairs + MLE_TILE - 1) / MLE_TILE, MLE_MAX_PARTIALS);
-    DevBuf part_buf;   // blocks x 4 partial sums | the 4 results
-    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * 4 * eb));
-    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * 4 * P::W;
-    hipLaunchKernelGGL(sumcheck_round_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, pairs, single, a, part);
-    hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 4, part, res);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(s_out, res, 4 * eb, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    FrSum<P> sum;
+    ZK_HIP_RC(sum.alloc(fr_blocks(pairs), 4));
+    hipLaunchKernelGGL(sumcheck_round_kernel<P>, dim3(sum.blocks), dim3(MLE_TILE), 0, st, pairs, single, a, sum.part());
+    return sum.finish(s_out, st);
 }
 
 }  // namespace zkmi

@@ -13,8 +13,7 @@
 // Roofline: the quotient kernel reads 15 vectors and writes one (512 B per point) against 22 field products;
 // at ~1000 cycles per product per wave it is integer-multiply bound like everything else on this path.
 #include <vector>
-#include "common.hip.h"
-#include "fr_mem.hip.h"
+#include "fr_sum.hip.h"
 
 namespace zkmi {
 using mem::DevBuf;
@@ -143,9 +142,8 @@ __global__ __launch_bounds__(256) void quotient_kernel(uint64_t m, QuotientArgs<
     Fp<P> t2 = fp_add<P>(bg, fp_mul<P>(load_fr<P>(q.s2 + o), q.beta_m));
     Fp<P> t3 = fp_add<P>(cg, fp_mul<P>(load_fr<P>(q.s3 + o), q.beta_m));
     Fp<P> right = fp_mul<P>(fp_mul<P>(fp_mul<P>(fp_mul<P>(t1, t2), t3), zw), q.alpha_r4);
-    Fp<P> one_raw = fp_zero<P>();
-    one_raw.v[0] = 1;  // the integer 1 (vectors are canonical, not Montgomery)
-    Fp<P> bound = fp_mul<P>(fp_mul<P>(fp_sub<P>(z, one_raw), load_fr<P>(q.l1 + o)), q.alpha2_r2);
+    // z - 1 with the integer 1: vectors are canonical, not Montgomery
+    Fp<P> bound = fp_mul<P>(fp_mul<P>(fp_sub<P>(z, fp_raw_one<P>()), load_fr<P>(q.l1 + o)), q.alpha2_r2);
     Fp<P> total = fp_add<P>(fp_add<P>(g, fp_sub<P>(left, right)), bound);
     store_fr<P>(out + o, fp_reduce_full<P>(fp_mul<P>(total, q.zh_inv_m[i % q.period])));
 }
@@ -153,9 +151,9 @@ __global__ __launch_bounds__(256) void quotient_kernel(uint64_t m, QuotientArgs<
 // Horner evaluation split over threads: thread t evaluates its chunk of `chunk` coefficients at x and weighs it
 // with x^(t chunk); a workgroup adds its 256 values in LDS and stores one partial sum (canonical).
 template <class P>
-__global__ __launch_bounds__(256) void poly_eval_kernel(uint64_t n, uint32_t chunk, const uint32_t* __restrict__ coeffs, Fp<P> x_m,
-                                                        uint32_t* __restrict__ partial) {
-    __shared__ uint32_t lds[P::N][256];
+__global__ __launch_bounds__(MLE_TILE) void poly_eval_kernel(uint64_t n, uint32_t chunk, const uint32_t* __restrict__ coeffs, Fp<P> x_m,
+                                                             uint32_t* __restrict__ partial) {
+    __shared__ uint32_t lds[P::N][MLE_TILE];
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t lo = t * chunk;
     Fp<P> acc = fp_zero<P>();
@@ -165,26 +163,7 @@ __global__ __launch_bounds__(256) void poly_eval_kernel(uint64_t n, uint32_t chu
         uint32_t e[2] = {(uint32_t)lo, (uint32_t)(lo >> 32)};
         acc = fp_mul<P>(acc, fp_pow<P>(x_m, e, 2));
     }
-#pragma unroll
-    for (int l = 0; l < P::N; ++l) lds[l][threadIdx.x] = acc.v[l];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            Fp<P> u, v;
-#pragma unroll
-            for (int l = 0; l < P::N; ++l) { u.v[l] = lds[l][threadIdx.x]; v.v[l] = lds[l][threadIdx.x + s]; }
-            u = fp_add<P>(u, v);
-#pragma unroll
-            for (int l = 0; l < P::N; ++l) lds[l][threadIdx.x] = u.v[l];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        Fp<P> u;
-#pragma unroll
-        for (int l = 0; l < P::N; ++l) u.v[l] = lds[l][0];
-        store_fr<P>(partial + (size_t)blockIdx.x * P::W, fp_reduce_full<P>(u));
-    }
+    block_sum_store<P>(acc, lds, partial + (size_t)blockIdx.x * P::W);
 }
 
 // ---- scans over Fr (grand product, division by a linear factor) ---------------------------------------------
@@ -223,36 +202,28 @@ __global__ __launch_bounds__(256) void fr_scan_reduce_kernel(uint64_t n, uint32_
 
 // in place: partial[t] <- partial[0] o .. o partial[t-1]   (exclusive), count <= SCAN_MAX_PARTIALS, one workgroup
 template <class P, class Op>
-__global__ __launch_bounds__(256) void fr_scan_block_kernel(uint32_t count, uint32_t* __restrict__ partial) {
-    __shared__ uint32_t lds[P::N][256];
+__global__ __launch_bounds__(MLE_TILE) void fr_scan_block_kernel(uint32_t count, uint32_t* __restrict__ partial) {
+    __shared__ uint32_t lds[P::N][MLE_TILE];
     const uint32_t per = (count + 255) / 256;
     const uint32_t lo = threadIdx.x * per;
     const uint32_t hi = lo + per < count ? lo + per : count;
     Fp<P> acc = Op::template identity<P>();
     for (uint32_t k = lo; k < hi; ++k) acc = Op::template op<P>(acc, load_fr<P>(partial + (size_t)k * P::W));
-#pragma unroll
-    for (int l = 0; l < P::N; ++l) lds[l][threadIdx.x] = acc.v[l];
+    lds_put<P>(lds, threadIdx.x, acc);
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread totals
         Fp<P> other;
         const bool take = (int)threadIdx.x >= d;
-        if (take) {
-#pragma unroll
-            for (int l = 0; l < P::N; ++l) other.v[l] = lds[l][threadIdx.x - d];
-        }
+        if (take) other = lds_get<P>(lds, threadIdx.x - d);
         __syncthreads();
         if (take) {
             acc = Op::template op<P>(other, acc);
-#pragma unroll
-            for (int l = 0; l < P::N; ++l) lds[l][threadIdx.x] = acc.v[l];
+            lds_put<P>(lds, threadIdx.x, acc);
         }
         __syncthreads();
     }
     Fp<P> run = Op::template identity<P>();
-    if (threadIdx.x > 0) {
-#pragma unroll
-        for (int l = 0; l < P::N; ++l) run.v[l] = lds[l][threadIdx.x - 1];
-    }
+    if (threadIdx.x > 0) run = lds_get<P>(lds, threadIdx.x - 1);
     for (uint32_t k = lo; k < hi; ++k) {
         Fp<P> e = load_fr<P>(partial + (size_t)k * P::W);
         store_fr<P>(partial + (size_t)k * P::W, fp_reduce_full<P>(run));
@@ -333,9 +304,7 @@ static int grand_product_dev_impl(uint64_t n, const void* num, const void* den, 
     ZK_HIP(hipStreamSynchronize(st));
     Fp<P> d = fp_unpack<P>(dtot);  // product of all denominators, Montgomery
     if (fp_is_zero<P>(d)) return fail(ZK_ERR_ARG, "grand product: zero denominator");
-    Fp<P> one_raw = fp_zero<P>();
-    one_raw.v[0] = 1;
-    Fp<P> dinv = fp_reduce_full<P>(fp_mul<P>(fp_inv<P>(d), one_raw));  // canonical integer 1 / Dtot
+    Fp<P> dinv = fp_reduce_full<P>(fp_mul<P>(fp_inv<P>(d), fp_raw_one<P>()));  // canonical integer 1 / Dtot
     hipLaunchKernelGGL(grand_product_finish_kernel<P>, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, n + 1, pn, sd, dinv, (uint32_t*)out);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipStreamSynchronize(st));
@@ -349,7 +318,7 @@ static int div_linear_dev_impl(uint64_t n, const void* coeffs, const uint64_t* r
     uint32_t* r = reinterpret_cast<uint32_t*>(rem);
     for (int k = 0; k < P::W; ++k) r[k] = 0;
     if (n == 0) return ZK_OK;
-    Fp<P> root_m = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(root_c));
+    Fp<P> root_m = fr_mont<P>(root_c);
     if (fp_is_zero<P>(root_m)) {  // division by X: a shift
         ZK_HIP(hipMemcpyAsync(r, coeffs, eb, hipMemcpyDeviceToHost, st));
         if (n > 1) ZK_HIP(hipMemcpyAsync(q, (const uint32_t*)coeffs + P::W, (n - 1) * eb, hipMemcpyDeviceToDevice, st));
@@ -458,7 +427,7 @@ static int quotient_impl(uint64_t m, uint64_t n, const void* const* cols, const 
     q.beta_m = scalar_times_r<P>(beta, 1);
     q.gamma = scalar_in<P>(gamma);
     q.alpha_r4 = scalar_times_r<P>(alpha, 4);
-    Fp<P> am = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(alpha));
+    Fp<P> am = fr_mont<P>(alpha);
     Fp<P> a2 = fp_mul<P>(am, am);  // alpha^2 R
     q.alpha2_r2 = fp_reduce_full<P>(fp_mul<P>(a2, fp_const<P>(P::R2)));
     for (uint32_t k = 0; k < QUOT_MAX_PERIOD; ++k)
@@ -479,8 +448,7 @@ static int poly_eval_impl_dev(uint64_t n, const void* coeffs, const uint64_t* x,
     DevBuf dpart;
     ZK_HIP_RC(dpart.alloc((size_t)blocks * P::W * 4));
     std::vector<uint32_t> part((size_t)blocks * P::W);
-    hipLaunchKernelGGL(poly_eval_kernel<P>, dim3(blocks), dim3(256), 0, st, n, chunk, (const uint32_t*)coeffs,
-                       fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(x)), dpart.as());
+    hipLaunchKernelGGL(poly_eval_kernel<P>, dim3(blocks), dim3(256), 0, st, n, chunk, (const uint32_t*)coeffs, fr_mont<P>(x), dpart.as());
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipMemcpyAsync(part.data(), dpart.as(), part.size() * 4, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
@@ -509,7 +477,7 @@ static int poly_eval_many_impl(int k, const uint64_t* counts, const void* const*
     for (int i = 0; i < k; ++i)
         if (counts[i])
             hipLaunchKernelGGL(poly_eval_kernel<P>, dim3(blocks[i]), dim3(256), 0, st, counts[i], chunk, (const uint32_t*)coeffs[i],
-                               fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(xs + (size_t)i * (P::W / 2))), dpart.as() + (size_t)first[i] * P::W);
+                               fr_mont<P>(xs + (size_t)i * (P::W / 2)), dpart.as() + (size_t)first[i] * P::W);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipMemcpyAsync(part.data(), dpart.as(), part.size() * 4, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));

@@ -14,32 +14,19 @@
 //
 // Like ipa.hip the kernels keep data canonical and carry host scalars in Montgomery form: mont(x, s R) = x s.  A product of two
 // canonical values carries R^-1, which the sums close once per thread with R^2.
-#include <algorithm>
-#include "common.hip.h"
-#include "fr_mem.hip.h"
-#include "fr_sum.hip.h"
+#include "ipa_chain.hip.h"
 
 namespace zkmi {
-using mem::DevBuf;
 
 constexpr int RP_MAX_BITS_LOG = 7;           // bitsize <= 128: 2^i stays a plain integer below r
-constexpr unsigned RP_MAX_BLOCKS = 1024;     // the grid's cap (ipa.hip's)
-constexpr int RP_SEED_BITS = 18;             // log2(RP_MAX_BLOCKS * MLE_TILE): a thread's first index has at most this many bits
-static_assert((1u << RP_SEED_BITS) == RP_MAX_BLOCKS * MLE_TILE, "the step of a power is the stride of the capped grid");
+constexpr int RP_SEED_BITS = 18;             // log2(FR_MAX_BLOCKS * MLE_TILE): a thread's first index has at most this many bits
+static_assert((1u << RP_SEED_BITS) == FR_MAX_BLOCKS * MLE_TILE, "the step of a power is the stride of the capped grid");
 
 // g^(2^t) R for t <= RP_SEED_BITS; the last one is the step of a grid-stride loop
 template <class P>
 struct RpPowers {
     Fp<P> sq[RP_SEED_BITS + 1];
 };
-
-// the integer 1 (not Montgomery form): the canonical one, and mont(x R, 1) = x
-template <class P>
-ZK_HD Fp<P> rp_raw_one() {
-    Fp<P> o = fp_zero<P>();
-    o.v[0] = 1;
-    return o;
-}
 
 // acc g^e for e < 2^bits
 template <class P>
@@ -71,7 +58,7 @@ template <class P>
 __global__ __launch_bounds__(MLE_TILE) void rp_bits_kernel(uint64_t n_pos, int log_bits, const uint64_t* __restrict__ values,
                                                            uint32_t* __restrict__ out) {
     const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
-    const Fp<P> zero = fp_zero<P>(), one = rp_raw_one<P>();
+    const Fp<P> zero = fp_zero<P>(), one = fp_raw_one<P>();
     Fp<P> minus_one = fp_const<P>(P::M);
     minus_one.v[0] -= 1;   // r is odd
     for (uint64_t k = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; k < n_pos; k += stride) {
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(MLE_TILE) void rp_eval_kernel(uint64_t n_pos, int l
                                                            uint32_t* __restrict__ ab, uint32_t* __restrict__ h_weight) {
     const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE;
     const Fp<P> y_step = c.y.sq[RP_SEED_BITS], yi_step = y_inv.sq[RP_SEED_BITS], z_step = c.z.sq[RP_SEED_BITS - log_bits];
-    const Fp<P> one = rp_raw_one<P>();
+    const Fp<P> one = fp_raw_one<P>();
     uint64_t k = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x;
     Fp<P> yk = rp_power<P>(c.y, k, seed_bits, fp_one<P>());
     Fp<P> yik = rp_power<P>(y_inv, k, seed_bits, fp_one<P>());
@@ -154,13 +141,13 @@ __global__ __launch_bounds__(MLE_TILE) void rp_eval_kernel(uint64_t n_pos, int l
 
 template <class P>
 struct RpVerifyArgs {
-    Fp<P> u_m[ZK_IPA_MAX_LOG], ui_m[ZK_IPA_MAX_LOG];  // u_t R, u_t^-1 R
+    IpaChain<P> c;              // first: the layout of the argument block is the flat one's
     RpPowers<P> y_inv, z;
-    Fp<P> a, b;                                       // the proof's scalars, below 2r
-    Fp<P> z2_m, z_c, neg_z;                           // z^2 R; z and -z, canonical, below 2r
+    Fp<P> a, b;                 // the proof's scalars, below 2r
+    Fp<P> z2_m, z_c, neg_z;     // z^2 R; z and -z, canonical, below 2r
 };
 
-// out[k] = -z - a s_k,  out[N+k] = z + y_inv^k (z^(2+j) 2^i - b s_k^-1): the chains of ipa_verify_scalars_kernel (2 log N products)
+// out[k] = -z - a s_k,  out[N+k] = z + y_inv^k (z^(2+j) 2^i - b s_k^-1): the challenge chain of ipa_chain.hip.h (2 log N products)
 // and 4 more per element
 template <class P>
 __global__ __launch_bounds__(MLE_TILE) void rp_verify_scalars_kernel(uint64_t n_pos, int log_n, int log_bits, int seed_bits, RpVerifyArgs<P> v,
@@ -173,11 +160,7 @@ __global__ __launch_bounds__(MLE_TILE) void rp_verify_scalars_kernel(uint64_t n_
     for (; k < n_pos; k += stride) {
         const unsigned i = (unsigned)(k & ((1u << log_bits) - 1));
         Fp<P> sa = v.a, sb = v.b;
-        for (int t = 0; t < log_n; ++t) {
-            const bool bit = (k >> (log_n - 1 - t)) & 1;
-            sa = fp_mul<P>(sa, bit ? v.u_m[t] : v.ui_m[t]);
-            sb = fp_mul<P>(sb, bit ? v.ui_m[t] : v.u_m[t]);
-        }
+        ipa_chain_run<P>(v.c, log_n, k, sa, sb);
         const Fp<P> h = fp_mul<P>(yik, fp_sub<P>(fp_mul<P>(zj, rp_two_pow<P>(i)), sb));
         store_fr<P>(out + k * P::W, fp_reduce_full<P>(fp_sub<P>(v.neg_z, sa)));
         store_fr<P>(out + (n_pos + k) * P::W, fp_reduce_full<P>(fp_add<P>(v.z_c, h)));
@@ -188,10 +171,6 @@ __global__ __launch_bounds__(MLE_TILE) void rp_verify_scalars_kernel(uint64_t n_
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-static unsigned rp_blocks(uint64_t items) {
-    return (unsigned)std::min<uint64_t>((items + MLE_TILE - 1) / MLE_TILE, RP_MAX_BLOCKS);
-}
-
 static int rp_check_sizes(const char* who, int log_bits, int log_n) {
     if (log_bits < 0 || log_bits > RP_MAX_BITS_LOG || log_n < log_bits || log_n > ZK_IPA_MAX_LOG)
         return fail(ZK_ERR_ARG, std::string(who) + ": need 0 <= log_bits <= 7 and log_bits <= log_N <= 22");
@@ -199,20 +178,9 @@ static int rp_check_sizes(const char* who, int log_bits, int log_n) {
 }
 
 template <class P>
-static Fp<P> rp_mont(const uint64_t* x) {
-    return fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(x));
-}
-
-// x mod r as an integer, below 2r
-template <class P>
-static Fp<P> rp_canon(const uint64_t* x) {
-    return fp_mul<P>(rp_mont<P>(x), rp_raw_one<P>());
-}
-
-template <class P>
 static RpPowers<P> rp_squarings(const uint64_t* g) {
     RpPowers<P> out;
-    out.sq[0] = rp_mont<P>(g);
+    out.sq[0] = fr_mont<P>(g);
     for (int t = 1; t <= RP_SEED_BITS; ++t) out.sq[t] = fp_mul<P>(out.sq[t - 1], out.sq[t - 1]);
     return out;
 }
@@ -223,7 +191,7 @@ static RpProverArgs<P> rp_prover_args(const uint64_t* y, const uint64_t* z) {
     c.y = rp_squarings<P>(y);
     c.z = rp_squarings<P>(z);
     c.z2_m = c.z.sq[1];
-    const Fp<P> one = rp_raw_one<P>(), zc = rp_canon<P>(z);
+    const Fp<P> one = fp_raw_one<P>(), zc = fr_canon<P>(z);
     c.l0[0] = fp_neg<P>(zc);
     c.l0[1] = fp_sub<P>(one, zc);
     c.ar_z[0] = fp_sub<P>(zc, one);
@@ -239,7 +207,7 @@ static int rp_bits_impl(int log_bits, int log_n, const void* d_values, void* d_o
     if (!d_values || !d_out) return fail(ZK_ERR_ARG, "rp_bits: null pointer");
     const uint64_t n_pos = 1ull << log_n, m = n_pos >> log_bits;
     if (ranges_overlap(d_values, m * 16, d_out, 2 * n_pos * P::W * 4)) return fail(ZK_ERR_ARG, "rp_bits: two buffers overlap");
-    hipLaunchKernelGGL(rp_bits_kernel<P>, dim3(rp_blocks(n_pos)), dim3(MLE_TILE), 0, st, n_pos, log_bits, (const uint64_t*)d_values,
+    hipLaunchKernelGGL(rp_bits_kernel<P>, dim3(fr_blocks(n_pos)), dim3(MLE_TILE), 0, st, n_pos, log_bits, (const uint64_t*)d_values,
                        (uint32_t*)d_out);
     ZK_HIP(hipGetLastError());
     return ZK_OK;
@@ -250,18 +218,12 @@ static int rp_poly_impl(int log_bits, int log_n, const void* d_values, const voi
                         hipStream_t st) {
     ZK_HIP_RC(rp_check_sizes("rp_poly", log_bits, log_n));
     if (!d_values || !d_s || !y || !z || !t_out) return fail(ZK_ERR_ARG, "rp_poly: null pointer");
-    const uint64_t n_pos = 1ull << log_n, eb = P::W * 4;
-    const unsigned blocks = rp_blocks(n_pos);
-    DevBuf part_buf;   // blocks x 3 partial sums | the 3 results
-    ZK_HIP_RC(part_buf.alloc((size_t)(blocks + 1) * 3 * eb));
-    uint32_t *const part = part_buf.as(), *res = part + (size_t)blocks * 3 * P::W;
-    hipLaunchKernelGGL(rp_poly_kernel<P>, dim3(blocks), dim3(MLE_TILE), 0, st, n_pos, log_bits, rp_seed_bits(log_n), rp_prover_args<P>(y, z),
-                       (const uint64_t*)d_values, (const uint32_t*)d_s, part);
-    hipLaunchKernelGGL(mle_combine_kernel<P>, dim3(1), dim3(MLE_TILE), 0, st, blocks, 3, part, res);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(t_out, res, 3 * eb, hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    return ZK_OK;
+    const uint64_t n_pos = 1ull << log_n;
+    FrSum<P> sum;
+    ZK_HIP_RC(sum.alloc(fr_blocks(n_pos), 3));
+    hipLaunchKernelGGL(rp_poly_kernel<P>, dim3(sum.blocks), dim3(MLE_TILE), 0, st, n_pos, log_bits, rp_seed_bits(log_n), rp_prover_args<P>(y, z),
+                       (const uint64_t*)d_values, (const uint32_t*)d_s, sum.part());
+    return sum.finish(t_out, st);
 }
 
 template <class P>
@@ -273,10 +235,9 @@ static int rp_eval_impl(int log_bits, int log_n, const void* d_values, const voi
     const void* buf[4] = {d_ab, d_h_weight, d_s, d_values};
     const uint64_t len[4] = {2 * n_pos * eb, n_pos * eb, 2 * n_pos * eb, (n_pos >> log_bits) * 16};
     for (int o = 0; o < 2; ++o)       // an output against everything after it
-        for (int q = o + 1; q < 4; ++q)
-            if (ranges_overlap(buf[o], len[o], buf[q], len[q])) return fail(ZK_ERR_ARG, "rp_eval: two buffers overlap");
-    hipLaunchKernelGGL(rp_eval_kernel<P>, dim3(rp_blocks(n_pos)), dim3(MLE_TILE), 0, st, n_pos, log_bits, rp_seed_bits(log_n),
-                       rp_prover_args<P>(y, z), rp_squarings<P>(y_inv), rp_mont<P>(x), (const uint64_t*)d_values, (const uint32_t*)d_s,
+        if (overlaps_any(buf[o], len[o], buf + o + 1, len + o + 1, 3 - o)) return fail(ZK_ERR_ARG, "rp_eval: two buffers overlap");
+    hipLaunchKernelGGL(rp_eval_kernel<P>, dim3(fr_blocks(n_pos)), dim3(MLE_TILE), 0, st, n_pos, log_bits, rp_seed_bits(log_n),
+                       rp_prover_args<P>(y, z), rp_squarings<P>(y_inv), fr_mont<P>(x), (const uint64_t*)d_values, (const uint32_t*)d_s,
                        (uint32_t*)d_ab, (uint32_t*)d_h_weight);
     ZK_HIP(hipGetLastError());
     return ZK_OK;
@@ -288,19 +249,16 @@ static int rp_verify_scalars_impl(int log_bits, int log_n, const uint64_t* u, co
     ZK_HIP_RC(rp_check_sizes("rp_verify_scalars", log_bits, log_n));
     if (!a || !b || !y_inv || !z || !d_out || (log_n && (!u || !u_inv))) return fail(ZK_ERR_ARG, "rp_verify_scalars: null argument");
     RpVerifyArgs<P> v;
-    for (int t = 0; t < ZK_IPA_MAX_LOG; ++t) {
-        v.u_m[t] = t < log_n ? rp_mont<P>(u + 4 * t) : fp_zero<P>();
-        v.ui_m[t] = t < log_n ? rp_mont<P>(u_inv + 4 * t) : fp_zero<P>();
-    }
+    v.c = ipa_chain_fill<P>(log_n, u, u_inv);
     v.y_inv = rp_squarings<P>(y_inv);
     v.z = rp_squarings<P>(z);
-    v.a = rp_canon<P>(a);
-    v.b = rp_canon<P>(b);
+    v.a = fr_canon<P>(a);
+    v.b = fr_canon<P>(b);
     v.z2_m = v.z.sq[1];
-    v.z_c = rp_canon<P>(z);
+    v.z_c = fr_canon<P>(z);
     v.neg_z = fp_neg<P>(v.z_c);
     const uint64_t n_pos = 1ull << log_n;
-    hipLaunchKernelGGL(rp_verify_scalars_kernel<P>, dim3(rp_blocks(n_pos)), dim3(MLE_TILE), 0, st, n_pos, log_n, log_bits, rp_seed_bits(log_n), v,
+    hipLaunchKernelGGL(rp_verify_scalars_kernel<P>, dim3(fr_blocks(n_pos)), dim3(MLE_TILE), 0, st, n_pos, log_n, log_bits, rp_seed_bits(log_n), v,
                        (uint32_t*)d_out);
     ZK_HIP(hipGetLastError());
     return ZK_OK;
