@@ -109,7 +109,9 @@ int zk_stream_synchronize(void* stream);
 int zk_fq_limbs(int curve);         /* 64-bit limbs per base-field element: 4 / 6 */
 int zk_point_limbs(int curve, int group); /* 64-bit limbs per affine point */
 
-/* ---- scalar-field vectors (polynomial_bn254 / polynomial_bls12_381 submodules) ---------- */
+/* ---- scalar-field vectors (polynomial_bn254 / polynomial_bls12_381 submodules) ----------
+ * csrc/ntt.hip: the transforms and the QAP chain (zk_ntt*, zk_qap_*); csrc/frvec.hip: the element-wise operations
+ * (zk_vec_*, zk_poly_div_vanishing); csrc/spmv.hip: the sparse products (zk_spmv_*). */
 
 /* fft / ifft / coset_fft / coset_ifft (src/bn254/polynomial.rs:535-585).
  * `in` holds n_in elements; the domain is next_pow2(size); the input is zero-padded, or, when
@@ -346,7 +348,8 @@ int zk_points_compress(int curve, int group, uint64_t n, const uint64_t* points,
 int zk_points_decompress(int curve, int group, uint64_t n, const uint8_t* in, uint64_t* out, uint64_t* bad_index);
 int zk_point_bytes(int curve, int group);
 
-/* ---- PlonK prover, device-resident vector kernels (csrc/plonk.hip) ----
+/* ---- PlonK prover, device-resident vector kernels (csrc/plonk.hip; the generic zk_vec_* among them, which the other
+ * provers call too, in csrc/frvec.hip) ----
  * They replace the element-wise polynomial arithmetic of Plonk.prove (python/zksnake/plonk/protocol.py:213-460: chains of
  * fft / mul_over_evaluation_domain / add_over_evaluation_domain, Polynomial scalar multiply-adds, Polynomial.__call__).
  * Vectors are canonical Fr elements in device memory; scalars are canonical 4-limb integers in host memory. */

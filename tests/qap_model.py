@@ -23,11 +23,12 @@ from helpers import rand_limbs
 from oracle import corc, pyref
 
 CURVES = (("BN254", 0), ("BLS12_381", 1))
-TILE_LOG, MAX_DIGIT = 11, 8      # NTT_TILE_LOG, NTT_MAX_DIGIT of csrc/ntt.hip
+TILE_LOG, MAX_DIGIT = 11, 8      # NTT_TILE_LOG, NTT_MAX_DIGIT of csrc/ntt_plan.h
 
 
 def plan(log_n):
-    """[(stages m, run length exponent q)] of the passes ntt_dev_impl launches for a 2^log_n transform"""
+    """[(stages m, run length exponent q)] of the passes ntt_dev_impl launches for a 2^log_n transform: ntt_plan of csrc/ntt_plan.h, restated
+    (tests/test_host_lib.py compares the two on the CPU)"""
     if log_n == 0:
         return []
     passes = 1 if log_n <= TILE_LOG else -(-log_n // MAX_DIGIT)

@@ -1,4 +1,4 @@
-"""Integer model of the sparse witness products (spmv_kernel, spmv_items_kernel, spmv_rows_kernel of csrc/ntt.hip) and the
+"""Integer model of the sparse witness products (spmv_kernel, spmv_items_kernel, spmv_rows_kernel of csrc/spmv.hip) and the
 fixtures their tests share.  Python integers, numpy and oracle.pyref only: nothing of the package is imported, so the cutter,
 the products and the thresholds below are restated here and pinned against the package on the CPU (tests/test_spmv_model.py).
 

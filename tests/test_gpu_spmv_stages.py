@@ -1,4 +1,4 @@
-"""GPU: the three sparse-product kernels of csrc/ntt.hip (spmv_kernel, spmv_items_kernel, spmv_rows_kernel) through their C
+"""GPU: the three sparse-product kernels of csrc/spmv.hip (spmv_kernel, spmv_items_kernel, spmv_rows_kernel) through their C
 entry points, against the integer model (tests/spmv_model.py), by ==.
 
 Every case pre-fills the output and the partial sums with garbage that is no field element (top bits set: above both moduli),

@@ -245,6 +245,23 @@ def test_dev_buf_gives_every_block_back_exactly_once(tmp_path):
     assert res.returncode == 0 and res.stdout.count(": ok") == 7 and "all ok" in res.stdout, res.stdout + res.stderr
 
 
+def test_ntt_pass_plan_equals_its_integer_model(tmp_path):
+    """ntt_plan (csrc/ntt_plan.h), which ntt_dev_impl loops over, printed for log_n = 0 .. 30 by tests/native/ntt_plan_check.cpp
+    and compared line by line with qap_model.plan, the copy the GPU chain tests derive their sizes from.  A host program under
+    the address and undefined-behaviour sanitizers, their runtimes linked in; no GPU and no device code."""
+    import subprocess
+    import qap_model
+    exe = str(tmp_path / "ntt_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                           "-static-libubsan", "-o", exe, os.path.join(ROOT, "tests", "native", "ntt_plan_check.cpp")])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stdout + res.stderr
+    lines = res.stdout.splitlines()
+    assert len(lines) == 31
+    for log_n, line in enumerate(lines):
+        assert line == f"{log_n}:" + "".join(f" {m},{q}" for m, q in qap_model.plan(log_n)), line
+
+
 def test_protocol_host_sides_refuse_bad_arguments_under_sanitizers(tmp_path):
     """the host side of csrc/ipa.hip and csrc/rangeproof.hip (argument rules, overlap checks, the conversion of the challenges,
     the shared pieces of fr_sum.hip.h and ipa_chain.hip.h) as two stand-alone programs under the address and undefined-behaviour

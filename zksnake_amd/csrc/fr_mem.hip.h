@@ -1,6 +1,6 @@
 // fr_mem.hip.h -- load / store of one scalar-field element between HBM (W packed 32-bit words, 16-byte vector
 // accesses) and registers (N 29-bit limbs).  Shared by ntt.hip and, through fr_sum.hip.h, every protocol file over Fr
-// (plonk.hip, mle.hip, ipa.hip, rangeproof.hip, gkr.hip).
+// (plonk.hip, frvec.hip, spmv.hip, mle.hip, ipa.hip, rangeproof.hip, gkr.hip).
 #pragma once
 #include "common.hip.h"
 

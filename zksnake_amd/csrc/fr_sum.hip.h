@@ -1,7 +1,7 @@
-// fr_sum.hip.h -- what the protocol kernels over Fr (mle.hip, ipa.hip, rangeproof.hip, gkr.hip, plonk.hip) share: the tile they
-// are launched with, the capped strided grid, host scalars into kernel arguments, and exact, repeatable sums over a grid of any
-// size: every workgroup of MLE_TILE threads adds its values in a fixed tree and stores one canonical partial sum, and ONE
-// workgroup adds the partial sums (mle_combine_kernel; FrSum is the host side of that).
+// fr_sum.hip.h -- what the kernels over Fr (mle.hip, ipa.hip, rangeproof.hip, gkr.hip, plonk.hip, frvec.hip, spmv.hip) share: the
+// tile they are launched with, the capped strided grid, host scalars into kernel arguments, and exact, repeatable sums over a grid
+// of any size: every workgroup of MLE_TILE threads adds its values in a fixed tree (block_sum) and stores one canonical partial
+// sum, and ONE workgroup adds the partial sums (mle_combine_kernel; FrSum is the host side of that).
 #pragma once
 #include <algorithm>
 #include "common.hip.h"
@@ -29,6 +29,18 @@ template <class P>
 static Fp<P> fr_canon(const uint64_t* x) {
     return fp_mul<P>(fr_mont<P>(x), fp_raw_one<P>());
 }
+// a CANONICAL host scalar as it is: the integer as limbs
+template <class P>
+__host__ Fp<P> scalar_in(const uint64_t* s) {
+    return fp_unpack<P>(reinterpret_cast<const uint32_t*>(s));
+}
+// s * R^k as an integer (k >= 0): what mont() must be fed to undo k divisions by R
+template <class P>
+__host__ Fp<P> scalar_times_r(const uint64_t* s, int k) {
+    Fp<P> v = scalar_in<P>(s);
+    for (int i = 0; i < k; ++i) v = fp_mul<P>(v, fp_const<P>(P::R2));
+    return fp_reduce_full<P>(v);
+}
 
 template <class P>
 __device__ __forceinline__ void lds_put(uint32_t (*lds)[MLE_TILE], int i, const Fp<P>& a) {
@@ -43,9 +55,11 @@ __device__ __forceinline__ Fp<P> lds_get(uint32_t (*lds)[MLE_TILE], int i) {
     return a;
 }
 
-// the workgroup's MLE_TILE values are added in a fixed tree and thread 0 stores the canonical sum (exact and the same on every run)
+// the workgroup's MLE_TILE values are added in a fixed tree (exact and the same on every run).  Afterwards element 0 of the tile
+// holds the sum, below 2r: thread 0 reads it with lds_get<P>(lds, 0).  (It is left in the tile and not returned so that the read
+// stays inside the caller's `threadIdx.x == 0` branch: returned, it changed the code of every kernel that stores the sum.)
 template <class P>
-__device__ __forceinline__ void block_sum_store(const Fp<P>& acc, uint32_t (*lds)[MLE_TILE], uint32_t* dst) {
+__device__ __forceinline__ void block_sum(const Fp<P>& acc, uint32_t (*lds)[MLE_TILE]) {
     __syncthreads();  // the tile may still be read from an earlier use
     lds_put<P>(lds, threadIdx.x, acc);
     __syncthreads();
@@ -53,6 +67,11 @@ __device__ __forceinline__ void block_sum_store(const Fp<P>& acc, uint32_t (*lds
         if ((int)threadIdx.x < s) lds_put<P>(lds, threadIdx.x, fp_add<P>(lds_get<P>(lds, threadIdx.x), lds_get<P>(lds, threadIdx.x + s)));
         __syncthreads();
     }
+}
+// ... and thread 0 stores the canonical sum
+template <class P>
+__device__ __forceinline__ void block_sum_store(const Fp<P>& acc, uint32_t (*lds)[MLE_TILE], uint32_t* dst) {
+    block_sum<P>(acc, lds);
     if (threadIdx.x == 0) store_fr<P>(dst, fp_reduce_full<P>(lds_get<P>(lds, 0)));
 }
 

@@ -10,7 +10,7 @@
 //   wiring evaluation  add~(r,u,v), mul~(r,u,v) = sum over ADD (MUL) gates of E_r[a] E_u[b] E_v[c]
 // A gate is (type u8: 0 ADD, 1 MUL; in1 u32; in2 u32); the host has checked in1, in2 < n_(j-1) when it compiled the circuit, so
 // the gathers below never leave their tables.  The two phases read the gates through a static CSR (grouped by in1 for phase 1,
-// by in2 for phase 2) whose rows are split by length as spmv_kernel's are (ntt.hip): one lane per short row; a row longer than
+// by in2 for phase 2) whose rows are split by length as spmv_kernel's are (spmv.hip): one lane per short row; a row longer than
 // GKR_LONG_ROW is cut on the host into work items, one workgroup sums each item and one workgroup then adds up each long row.
 // Every row is written by exactly one thread, empty rows as zero: no atomics, and the outputs never need clearing.
 //

@@ -1,9 +1,8 @@
-// ntt.hip -- scalar-field radix-2 NTT / iNTT, element-wise vector ops and the fused QAP
-// quotient pipeline for BN254 Fr and BLS12-381 Fr on gfx950.
+// ntt.hip -- scalar-field radix-2 NTT / iNTT and the fused QAP quotient pipeline built on it, for BN254 Fr and
+// BLS12-381 Fr on gfx950.  (The element-wise vector operations are in frvec.hip, the sparse products in spmv.hip.)
 //
-// Stands in for fft/ifft/coset_fft/coset_ifft, add/mul_over_evaluation_domain and
-// Polynomial.divide_by_vanishing_poly of the reference (src/bn254/polynomial.rs:466-489,
-// 535-634 and the bls12_381 twin), which call ark-poly 0.4.2's Radix2EvaluationDomain.
+// Stands in for fft/ifft/coset_fft/coset_ifft of the reference (src/bn254/polynomial.rs:535-634 and the bls12_381
+// twin), which call ark-poly 0.4.2's Radix2EvaluationDomain.
 //
 // Layout in HBM: a vector is 2^k elements x 8 u32 (32 B), canonical integers, natural order.
 // The transform is linear, so it runs directly on canonical data with twiddles kept in
@@ -20,11 +19,11 @@
 #include "common.hip.h"
 #include "fr_mem.hip.h"
 #include "ntt_lazy.hip.h"
+#include "ntt_plan.h"
 
 namespace zkmi {
 using mem::DevBuf;
 
-constexpr int NTT_TILE_LOG = 11;   // 2048 elements = 72 KiB of LDS per workgroup (limb-major), two workgroups per CU
 #ifndef NTT_THREADS_N
 #define NTT_THREADS_N 512
 #endif
@@ -32,35 +31,13 @@ constexpr int NTT_TILE_LOG = 11;   // 2048 elements = 72 KiB of LDS per workgrou
 #define NTT_MIN_BLOCKS 2
 #endif
 constexpr int NTT_THREADS = NTT_THREADS_N;
-constexpr int NTT_MAX_DIGIT = 8;   // stages per pass: 2^8 x 2^3 runs of 256 B at least
+static_assert(NTT_THREADS % 64 == 0, "whole waves: the pass kernel's barrier-free steps count on wave w holding threads [64w, 64w + 64)");
 
 // ---- twiddle generation -------------------------------------------------------------------
 // Stage-major table, independent of the transform size: stage s of a DIF transform pairs (i, i + 2^s) and multiplies the
 // difference by zeta_{s+1}^(i mod 2^s), zeta_k = primitive 2^k-th root of unity.  Row s holds zeta_{s+1}^j, j < 2^s, at
 // offset 2^s - 1: consecutive butterflies read consecutive entries (the former single table w_n^k made every butterfly of
-// a low stage fetch its own 64-byte sector: one L2 request each).
-template <class P>
-__global__ void twiddle_kernel(uint32_t* out, Fp<P> zeta, uint32_t count) {
-    uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    uint32_t e[1] = {k};
-    Fp<P> r = fp_pow<P>(zeta, e, 1);
-    store_fr<P>(out + (size_t)k * P::W, r);
-}
-
-// out[k] = g^k as canonical integers (setup: the powers of tau), square-and-multiply per element
-template <class P>
-__global__ void powers_kernel(uint32_t* out, Fp<P> g, uint32_t count) {
-    uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    uint32_t e[1] = {k};
-    Fp<P> r = fp_pow<P>(g, e, 1);
-    uint32_t w[P::W];
-    fp_to_canonical<P>(w, r);
-    uint4* q = reinterpret_cast<uint4*>(out + (size_t)k * P::W);
-#pragma unroll
-    for (int i = 0; i < P::W / 4; ++i) q[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-}
+// a low stage fetch its own 64-byte sector: one L2 request each).  twiddle9_kernel below fills it.
 
 // the lazy-range arithmetic of the butterfly passes (lz_add, lz_sub, lz_norm, lz_reduce, lz_canonical) is in ntt_lazy.hip.h
 
@@ -242,7 +219,8 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_MIN_BLOCKS) void ntt_pass_kernel(c
         // A step on element bits (pos_lo, pos_lo + 1) with pos_lo <= 6 stays inside blocks of 256 consecutive elements, and with
         // one element quad per lane (tile / 4 == NTT_THREADS) wave w holds exactly block w: when this step and the next are both of
         // that kind the next one reads only what this wave wrote, and the LDS serves one wave's accesses in order -- no workgroup
-        // barrier, the waves drift apart for two steps (the last two steps of a pass with q = 3)
+        // barrier, the waves drift apart for two steps (the last two steps of a pass with q = 3).
+        // The branch relies on three things: wave64, one element quad per lane, and wave w owning elements [256w, 256w + 256).
         const bool wave_private = (tile >> 2) == NTT_THREADS && pos_lo <= 6 && b >= 3;
         if (wave_private) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         else __syncthreads();
@@ -300,156 +278,105 @@ __global__ void coset_scale_kernel(uint32_t* data, const uint32_t* tw, uint32_t 
     store_fr<P>(data + (size_t)i * P::W, fp_reduce_full<P>(fp_mul<P>(a, w)));
 }
 
-// op: 0 mul, 1 add, 2 sub on canonical data.  mul: mont(mont(a,b), R^2) = a*b
-template <class P>
-__global__ void vec_op_kernel(int op, uint64_t n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fp<P> x = load_fr<P>(a + i * P::W), y = load_fr<P>(b + i * P::W), z;
-    if (op == 0) z = fp_mul<P>(fp_mul<P>(x, y), fp_const<P>(P::R2));
-    else if (op == 1) z = fp_add<P>(x, y);
-    else z = fp_sub<P>(x, y);
-    store_fr<P>(out + i * P::W, fp_reduce_full<P>(z));
-}
-
-// reduce every element below the modulus (inputs of the host API may be >= r)
-template <class P>
-__global__ void canon_kernel(uint64_t n, uint32_t* a) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t x[P::W];
-    uint4* q = reinterpret_cast<uint4*>(a + i * P::W);
-#pragma unroll
-    for (int k = 0; k < P::W / 4; ++k) {
-        uint4 t = q[k];
-        x[4 * k] = t.x; x[4 * k + 1] = t.y; x[4 * k + 2] = t.z; x[4 * k + 3] = t.w;
-    }
-    for (int k = 0; k < 10; ++k) {
-        uint32_t t[P::W];
-        if (fp_sub_mod_raw<P>(t, x)) break;
-#pragma unroll
-        for (int l = 0; l < P::W; ++l) x[l] = t[l];
-    }
-#pragma unroll
-    for (int k = 0; k < P::W / 4; ++k) q[k] = make_uint4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
-}
-
-// q[j] = sum_{k>=1} c[j + k n],  rem[i] = c[i] + q[i]   (c has len coefficients)
-template <class P>
-__global__ void div_vanishing_kernel(uint64_t n, uint64_t len, const uint32_t* c, uint32_t* q, uint32_t* rem,
-                                     int* nonzero) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t top = len < n ? len : n;
-    uint64_t qlen = len > n ? len - n : 0;
-    uint64_t lim = qlen > top ? qlen : top;
-    if (i >= lim) return;
-    // q[i] for i < qlen (may exceed n when len > 2n: then q[i] also folds further blocks)
-    Fp<P> acc = fp_zero<P>();
-    if (i < qlen) {
-        for (uint64_t j = i + n; j < len; j += n) acc = fp_add<P>(acc, load_fr<P>(c + j * P::W));
-        store_fr<P>(q + i * P::W, fp_reduce_full<P>(acc));
-    }
-    if (i < top) {
-        Fp<P> r = fp_reduce_full<P>(fp_add<P>(load_fr<P>(c + i * P::W), acc));
-        store_fr<P>(rem + i * P::W, r);
-        if (!fp_is_zero<P>(r)) atomicOr(nonzero, 1);
-    }
-}
-
-// CSR sparse matrix-vector product over Fr: out[row] = sum vals[k] * w[cols[k]].
-// Canonical in/out: mont(mont(v, x), R^2) = v*x; the sum is accumulated in Montgomery-by-R^-1 form
-// and fixed up once per row.
-// Short rows (the bulk of an R1CS) take one lane each.  A row longer than `skip_longer_than` is left to the long-row
-// kernels below: the constant-one wire and the input wires of a real circuit (and every row of the transposed matrices
-// that Groth16.setup multiplies) can hold 2^20 entries, and one lane walking them took 0.8 s.
-template <class P>
-__global__ void spmv_kernel(uint64_t n_rows, const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ cols,
-                            const uint32_t* __restrict__ vals, const uint32_t* __restrict__ w, uint32_t* __restrict__ out,
-                            uint32_t skip_longer_than) {
-    uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= n_rows) return;
-    const uint32_t k0 = row_ptr[row], k1 = row_ptr[row + 1];
-    if (skip_longer_than && k1 - k0 > skip_longer_than) return;
-    Fp<P> acc = fp_zero<P>();
-    for (uint32_t k = k0; k < k1; ++k) {
-        Fp<P> v = load_fr<P>(vals + (size_t)k * P::W);
-        Fp<P> x = load_fr<P>(w + (size_t)cols[k] * P::W);
-        acc = fp_add<P>(acc, fp_mul<P>(v, x));  // v*x/R
-    }
-    store_fr<P>(out + row * P::W, fp_reduce_full<P>(fp_mul<P>(acc, fp_const<P>(P::R2))));
-}
-
-// Long rows, two launches and no cross-workgroup hand-off: the host cuts every long row into work items [k0, k1) of at
-// most a few thousand entries (static per matrix); one workgroup per item leaves its partial sum (still v*x/R form,
-// semi-reduced) in `partials`; one workgroup per long row then adds up its items and writes the canonical result.
-constexpr int SPMV_LONG_THREADS = 256;
-
-template <class P>
-__device__ __forceinline__ Fp<P> block_sum_fr(Fp<P> acc, uint32_t* sh) {
-    constexpr int N = P::N;
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t off = SPMV_LONG_THREADS / 2; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int l = 0; l < N; ++l) sh[l * SPMV_LONG_THREADS + tid] = acc.v[l];
-        __syncthreads();
-        if (tid < off) {
-            Fp<P> o;
-#pragma unroll
-            for (int l = 0; l < N; ++l) o.v[l] = sh[l * SPMV_LONG_THREADS + tid + off];
-            acc = fp_add<P>(acc, o);
-        }
-        __syncthreads();
-    }
-    return acc;
-}
-
-template <class P>
-__global__ __launch_bounds__(SPMV_LONG_THREADS) void spmv_items_kernel(const uint32_t* __restrict__ items /* (k0, k1) pairs */,
-                                                                       const uint32_t* __restrict__ cols, const uint32_t* __restrict__ vals,
-                                                                       const uint32_t* __restrict__ w, uint32_t* __restrict__ partials) {
-    __shared__ uint32_t sh[P::N * SPMV_LONG_THREADS];
-    const uint32_t k0 = items[2 * blockIdx.x], k1 = items[2 * blockIdx.x + 1];
-    Fp<P> acc = fp_zero<P>();
-    for (uint32_t k = k0 + threadIdx.x; k < k1; k += SPMV_LONG_THREADS) {
-        Fp<P> v = load_fr<P>(vals + (size_t)k * P::W);
-        Fp<P> x = load_fr<P>(w + (size_t)cols[k] * P::W);
-        acc = fp_add<P>(acc, fp_mul<P>(v, x));
-    }
-    acc = block_sum_fr<P>(acc, sh);
-    if (threadIdx.x == 0) store_fr<P>(partials + (size_t)blockIdx.x * P::W, acc);
-}
-
-template <class P>
-__global__ __launch_bounds__(SPMV_LONG_THREADS) void spmv_rows_kernel(const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ item_ptr,
-                                                                      const uint32_t* __restrict__ partials, uint32_t* __restrict__ out) {
-    __shared__ uint32_t sh[P::N * SPMV_LONG_THREADS];
-    const uint32_t i0 = item_ptr[blockIdx.x], i1 = item_ptr[blockIdx.x + 1];
-    Fp<P> acc = fp_zero<P>();
-    for (uint32_t i = i0 + threadIdx.x; i < i1; i += SPMV_LONG_THREADS) acc = fp_add<P>(acc, load_fr<P>(partials + (size_t)i * P::W));
-    acc = block_sum_fr<P>(acc, sh);
-    if (threadIdx.x == 0) store_fr<P>(out + (size_t)long_rows[blockIdx.x] * P::W, fp_reduce_full<P>(fp_mul<P>(acc, fp_const<P>(P::R2))));
-}
-
-// QAP tail: flag |= (lo[i] + hi[i] - w[i] != 0)
-template <class P>
-__global__ void qap_check_kernel(uint64_t n, const uint32_t* lo, const uint32_t* hi, const uint32_t* w, int* nonzero) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fp<P> r = fp_sub<P>(fp_add<P>(load_fr<P>(lo + i * P::W), load_fr<P>(hi + i * P::W)), load_fr<P>(w + i * P::W));
-    if (!fp_is_zero<P>(r)) atomicOr(nonzero, 1);
-}
-
-// ---- host side ------------------------------------------------------------------------------
-
+// ---- host side: what the transforms keep between calls has ONE owner and ONE mutex -----------------------------------------------
 struct TwiddleSet {
     uint32_t* fwd = nullptr;
     uint32_t* inv = nullptr;
     int stages = 0;  // rows 0 .. stages-1 are built (enough for transforms up to 2^stages)
 };
+struct QapTabs {
+    uint32_t *fwd = nullptr, *inv = nullptr;   // g^i / N and -g^-i R / (2N) as canonical Montgomery representatives, g = w_2n
+};
+// Scratch vectors of the transform, one set per stream (work on a stream is ordered, so reuse is safe), grow-only; and the one
+// "u and v are final" event per stream (zk_qap_h_dev_begin, zk_qap_uv_dev)
+struct PerStream {
+    uint32_t* scratch = nullptr;
+    size_t bytes = 0;
+    hipEvent_t uv_ready = nullptr;
+};
 
-static std::mutex g_tw_mutex;
-static std::map<int, TwiddleSet> g_twiddles;          // per curve
-static std::vector<void*> g_tw_retired;               // smaller tables replaced by a bigger one: other streams may still read them
+// Two equal tables from plain hipMalloc (not the caching allocator: they stay until shutdown).  Both go back unless the builder
+// got as far as publishing them and called release(): a failing allocation, launch or synchronise leaks neither.
+struct TablePair {
+    uint32_t *a = nullptr, *b = nullptr;
+    TablePair() = default;
+    TablePair(const TablePair&) = delete;
+    TablePair& operator=(const TablePair&) = delete;
+    ~TablePair() { (void)hipFree(a); (void)hipFree(b); }
+    int alloc(size_t bytes) {
+        ZK_HIP(hipMalloc(&a, bytes));
+        ZK_HIP(hipMalloc(&b, bytes));
+        return ZK_OK;
+    }
+    void release() { a = b = nullptr; }
+};
+
+// Every member is read and written under `mutex`, and no function here takes it twice: get_qap_tabs calls get_twiddles FIRST and
+// locks afterwards.
+struct NttCaches {
+    std::mutex mutex;
+    std::map<int, TwiddleSet> twiddles;                    // per curve
+    std::vector<void*> retired;                            // smaller tables replaced by a bigger one: other streams may still read them, so they stay until shutdown
+    std::map<std::pair<int, int>, QapTabs> qap_tabs;       // (curve, log_n)
+    std::map<hipStream_t, PerStream> streams;
+
+    int scratch(hipStream_t stream, size_t bytes, uint32_t** out) {
+        std::lock_guard<std::mutex> lock(mutex);
+        PerStream& ps = streams[stream];
+        if (ps.bytes < bytes) {
+            if (ps.scratch) {
+                ZK_HIP(hipStreamSynchronize(stream));   // queued passes may still read the vectors that go
+                (void)hipFree(ps.scratch);
+                ps.scratch = nullptr;
+                ps.bytes = 0;
+            }
+            ZK_HIP(hipMalloc(&ps.scratch, bytes));
+            ps.bytes = bytes;
+        }
+        *out = ps.scratch;
+        return ZK_OK;
+    }
+
+    int uv_event(hipStream_t stream, hipEvent_t* out) {
+        std::lock_guard<std::mutex> lock(mutex);
+        PerStream& ps = streams[stream];
+        if (!ps.uv_ready) ZK_HIP(hipEventCreateWithFlags(&ps.uv_ready, hipEventDisableTiming));
+        *out = ps.uv_ready;
+        return ZK_OK;
+    }
+
+    // zk_shutdown
+    void free_all() {
+        std::lock_guard<std::mutex> lock(mutex);
+        for (auto& kv : twiddles) { (void)hipFree(kv.second.fwd); (void)hipFree(kv.second.inv); }
+        for (void* p : retired) (void)hipFree(p);
+        for (auto& kv : qap_tabs) { (void)hipFree(kv.second.fwd); (void)hipFree(kv.second.inv); }
+        for (auto& kv : streams) {
+            (void)hipFree(kv.second.scratch);
+            if (kv.second.uv_ready) (void)hipEventDestroy(kv.second.uv_ready);
+        }
+        twiddles.clear();
+        retired.clear();
+        qap_tabs.clear();
+        streams.clear();
+    }
+
+    // zk_stream_destroy: what is kept for this stream goes with it (it used to stay until zk_shutdown, and the next stream that was
+    // handed the same handle value inherited it).  The caller has synchronised the stream: nothing queued on it reads the scratch.
+    void release_stream(hipStream_t stream) {
+        PerStream ps;
+        {
+            std::lock_guard<std::mutex> lock(mutex);
+            auto it = streams.find(stream);
+            if (it == streams.end()) return;
+            ps = it->second;
+            streams.erase(it);
+        }
+        (void)hipFree(ps.scratch);
+        if (ps.uv_ready) (void)hipEventDestroy(ps.uv_ready);
+    }
+};
+static NttCaches g_ntt;
 
 template <class P>
 static Fp<P> host_root(int log_order, bool inverse) {
@@ -461,83 +388,43 @@ static Fp<P> host_root(int log_order, bool inverse) {
 
 template <class P>
 static int get_twiddles(int curve, int log_n, TwiddleSet* out, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(g_tw_mutex);
-    TwiddleSet& cur = g_twiddles[curve];
+    std::lock_guard<std::mutex> lock(g_ntt.mutex);
+    TwiddleSet& cur = g_ntt.twiddles[curve];
     if (cur.stages >= log_n) { *out = cur; return ZK_OK; }
     TwiddleSet ts;
     ts.stages = log_n < 16 ? 16 : log_n;  // small transforms share one 2 MiB table
     if (ts.stages > P::TWO_ADICITY) ts.stages = P::TWO_ADICITY;
-    const size_t bytes = (((size_t)1 << ts.stages) - 1) * TW_WORDS * 4;
-    ZK_HIP(hipMalloc(&ts.fwd, bytes));
-    hipError_t e_inv = hipMalloc(&ts.inv, bytes);
-    if (e_inv != hipSuccess) (void)hipFree(ts.fwd);
-    ZK_HIP(e_inv);
+    TablePair tabs;
+    ZK_HIP_RC(tabs.alloc((((size_t)1 << ts.stages) - 1) * TW_WORDS * 4));
     for (int s = 0; s < ts.stages; ++s) {
         const uint32_t count = 1u << s;
         const size_t off = ((size_t)count - 1) * TW_WORDS;
-        hipLaunchKernelGGL(twiddle9_kernel<P>, dim3((count + 255) / 256), dim3(256), 0, stream, ts.fwd + off, host_root<P>(s + 1, false), count);
-        hipLaunchKernelGGL(twiddle9_kernel<P>, dim3((count + 255) / 256), dim3(256), 0, stream, ts.inv + off, host_root<P>(s + 1, true), count);
+        hipLaunchKernelGGL(twiddle9_kernel<P>, dim3((count + 255) / 256), dim3(256), 0, stream, tabs.a + off, host_root<P>(s + 1, false), count);
+        hipLaunchKernelGGL(twiddle9_kernel<P>, dim3((count + 255) / 256), dim3(256), 0, stream, tabs.b + off, host_root<P>(s + 1, true), count);
     }
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipStreamSynchronize(stream));
-    if (cur.fwd) { g_tw_retired.push_back(cur.fwd); g_tw_retired.push_back(cur.inv); }
+    if (cur.fwd) { g_ntt.retired.push_back(cur.fwd); g_ntt.retired.push_back(cur.inv); }
+    ts.fwd = tabs.a;
+    ts.inv = tabs.b;
+    tabs.release();
     cur = ts;
     *out = ts;
     return ZK_OK;
 }
 
-static void free_scratch();
-static void free_coset_tables();
-static void free_uv_events();
-static void free_twiddles() {
-    free_uv_events();
-    std::lock_guard<std::mutex> lock(g_tw_mutex);
-    for (auto& kv : g_twiddles) {
-        (void)hipFree(kv.second.fwd);
-        (void)hipFree(kv.second.inv);
-    }
-    g_twiddles.clear();
-    for (void* p : g_tw_retired) (void)hipFree(p);
-    g_tw_retired.clear();
-    free_coset_tables();
-}
-
-// Scratch vectors of the transform, one set per stream (work on a stream is ordered, so reuse is safe); grow-only.
-struct NttScratch {
-    uint32_t* ptr = nullptr;
-    size_t bytes = 0;
-};
-static std::mutex g_scratch_mutex;
-static std::map<hipStream_t, NttScratch> g_scratch;
-
-static int get_scratch(hipStream_t stream, size_t bytes, uint32_t** out) {
-    std::lock_guard<std::mutex> lock(g_scratch_mutex);
-    NttScratch& sc = g_scratch[stream];
-    if (sc.bytes < bytes) {
-        if (sc.ptr) {
-            ZK_HIP(hipStreamSynchronize(stream));
-            (void)hipFree(sc.ptr);
-            sc.ptr = nullptr;
-            sc.bytes = 0;
-        }
-        ZK_HIP(hipMalloc(&sc.ptr, bytes));
-        sc.bytes = bytes;
-    }
-    *out = sc.ptr;
+// the pass kernel asks for more dynamic LDS than a kernel gets by default: once per field, under the owner's lock
+template <class P>
+static int allow_pass_lds() {
+    static bool set = false;   // one per field; a property of the loaded kernel, so it outlives free_all()
+    std::lock_guard<std::mutex> lock(g_ntt.mutex);
+    if (set) return ZK_OK;
+    ZK_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(P::N * ((1u << NTT_TILE_LOG) + 32) * 4)));
+    set = true;
     return ZK_OK;
 }
 
-static void free_scratch() {
-    std::lock_guard<std::mutex> lock(g_scratch_mutex);
-    for (auto& kv : g_scratch) (void)hipFree(kv.second.ptr);
-    g_scratch.clear();
-}
-
-// Pass plan: ceil(log_n / 8) passes, the stages split as evenly as possible with the larger digits LAST (the later
-// passes share one twiddle among the 2^q elements of a run and read small table rows; the first pass streams one twiddle
-// per butterfly).  2^22 = 7 + 7 + 8 stages on tiles of 128 x 16, 128 x 16 and 256 x 8 elements: every global access is a
-// run of 256 or 512 bytes.  Data flow: d -> scratch A -> scratch B -> ... -> d (a single pass runs in place: one
-// workgroup holds the whole vector).
 // what qap_h_dev_impl folds into a transform: NttFuse for the kernel, plus the vectors the first pass reads from (src, instead
 // of d) and the last pass writes to (dst, instead of d)
 template <class P>
@@ -549,19 +436,16 @@ struct NttPlanFuse {
     Fp<P> scale;
 };
 
+// One launch per pass of ntt_plan (ntt_plan.h).  Data flow: d -> scratch A -> scratch B -> ... -> d (a single pass runs in place:
+// one workgroup holds the whole vector).
 template <class P>
 static int ntt_dev_impl(int curve, int inverse, int log_n, uint32_t* d, hipStream_t stream, const NttPlanFuse<P>* fuse = nullptr) {
     if (log_n < 0 || log_n > P::TWO_ADICITY || log_n > 30) return fail(ZK_ERR_DOMAIN, "Domain size is too large");
     if (log_n == 0) return ZK_OK;
-    static bool attr_set = false;
-    if (!attr_set) {
-        ZK_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(P::N * ((1u << NTT_TILE_LOG) + 32) * 4)));
-        attr_set = true;
-    }
-    TwiddleSet ts;
-    int rc = get_twiddles<P>(curve, log_n, &ts, stream);
+    int rc = allow_pass_lds<P>();
     if (rc) return rc;
+    TwiddleSet ts;
+    if ((rc = get_twiddles<P>(curve, log_n, &ts, stream))) return rc;
     const uint32_t* tw = inverse ? ts.inv : ts.fwd;
     const size_t bytes = ((size_t)1 << log_n) * TW_WORDS * 4;   // a scratch vector: nine raw limb words per element
     Fp<P> scale = fp_one<P>();
@@ -571,38 +455,16 @@ static int ntt_dev_impl(int curve, int inverse, int log_n, uint32_t* d, hipStrea
         scale = fp_reduce_full<P>(fp_inv<P>(fp_from_canonical<P>(nn)));   // canonical: the last pass multiplies values < 9p by it
         if (fuse && fuse->own_scale) scale = fuse->scale;
     }
-    const int passes = log_n <= NTT_TILE_LOG ? 1 : (log_n + NTT_MAX_DIGIT - 1) / NTT_MAX_DIGIT;
+    NttPass plan[8];
+    const int passes = ntt_plan(log_n, plan);
     uint32_t* scratch = nullptr;
-    if (passes > 1 && (rc = get_scratch(stream, bytes * (passes > 2 ? 2 : 1), &scratch))) return rc;
+    if (passes > 1 && (rc = g_ntt.scratch(stream, bytes * (passes > 2 ? 2 : 1), &scratch))) return rc;
     uint32_t* bufs[2] = {scratch, scratch ? scratch + (bytes / 4) : nullptr};
     const uint32_t* src = fuse && fuse->src ? fuse->src : d;
     uint32_t* final_dst = fuse && fuse->dst ? fuse->dst : d;
     int rem = log_n, which = 0;
-    // Stages per pass.  An odd count costs a radix-2 step (616 instructions for one stage of four elements against 1054 for the two
-    // stages of a radix-4 step), so odd digits are paired up into even ones where the sum allows it, and the smallest digit goes in
-    // the middle (2^22: 8 + 6 + 8 runs 0.557 ms, 8 + 8 + 6 0.564, 6 + 8 + 8 0.571, the balanced 7 + 7 + 8 0.580-0.592)
-    int digits[8] = {0};
-    {
-        for (int i = 0, r = log_n; i < passes; ++i) { digits[i] = r / (passes - i); r -= digits[i]; }
-        for (;;) {
-            int a = -1, b = -1;
-            for (int i = 0; i < passes; ++i) if (digits[i] & 1) { if (a < 0) a = i; else if (b < 0) b = i; }
-            if (b < 0) break;
-            if (digits[a] < NTT_MAX_DIGIT) { ++digits[a]; --digits[b]; }
-            else if (digits[b] < NTT_MAX_DIGIT) { ++digits[b]; --digits[a]; }
-            else break;
-        }
-        std::sort(digits, digits + passes, [](int x, int y) { return x > y; });
-        if (passes >= 3) {   // smallest to the middle: rotate it in from the end
-            const int small = digits[passes - 1], mid = passes / 2;
-            for (int i = passes - 1; i > mid; --i) digits[i] = digits[i - 1];
-            digits[mid] = small;
-        }
-    }
     for (int i = 0; i < passes; ++i) {
-        const int m = digits[i];
-        const int rest_bits = log_n - m;
-        const int q = passes == 1 ? 0 : std::min(NTT_TILE_LOG - m, rest_bits);
+        const int m = plan[i].m, q = plan[i].q;
         const bool last = i == passes - 1;
         uint32_t* dst = last ? final_dst : bufs[which];
         const uint32_t tile = 1u << (m + q);
@@ -610,7 +472,7 @@ static int ntt_dev_impl(int curve, int inverse, int log_n, uint32_t* d, hipStrea
         NttFuse kf;
         if (fuse && i == 0) kf.in_v = fuse->k.in_v;
         if (fuse && last) { kf.scale_tab = fuse->k.scale_tab; kf.out2 = fuse->k.out2; kf.add_tab = fuse->k.add_tab; }
-        hipLaunchKernelGGL(ntt_pass_kernel<P>, dim3(1u << (rest_bits - q)), dim3(NTT_THREADS), lds_bytes, stream, src, dst, tw, log_n, rem, m, q,
+        hipLaunchKernelGGL(ntt_pass_kernel<P>, dim3(1u << (log_n - m - q)), dim3(NTT_THREADS), lds_bytes, stream, src, dst, tw, log_n, rem, m, q,
                            i > 0 ? 1 : 0, last ? 1 : 0, scale, (last && inverse) ? 1 : 0, kf);
         src = dst;
         which ^= 1;
@@ -633,14 +495,6 @@ static int coset_scale_impl(int curve, int inverse, int log_n, uint32_t* d, hipS
 }
 
 template <class P>
-static int vec_op_dev_impl(int op, uint64_t n, const uint32_t* a, const uint32_t* b, uint32_t* out, hipStream_t stream) {
-    if (n == 0) return ZK_OK;
-    hipLaunchKernelGGL(vec_op_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, op, n, a, b, out);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
-}
-
-template <class P>
 static int ntt_host_impl(int curve, int inverse, int coset, uint64_t n_in, const uint64_t* in, uint64_t size, uint64_t* out) {
     uint64_t n = next_pow2_u64(size == 0 ? 1 : size);
     int log_n = log2_u64(n);
@@ -657,53 +511,11 @@ static int ntt_host_impl(int curve, int inverse, int coset, uint64_t n_in, const
     uint32_t* const d = buf.as();
     ZK_HIP(hipMemset(d, 0, alloc * eb));
     if (n_in) ZK_HIP(hipMemcpy(d, in, n_in * eb, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((alloc + 255) / 256)), dim3(256), 0, 0, alloc, d);
+    ZK_HIP_RC(zk_vec_canon_dev(curve, alloc, d, nullptr));   // inputs of the host API may be >= r (frvec.hip)
     if (coset && !inverse) ZK_HIP_RC(coset_scale_impl<P>(curve, 0, log_n, d, 0));
     ZK_HIP_RC(ntt_dev_impl<P>(curve, inverse, log_n, d, 0));
     if (coset && inverse) ZK_HIP_RC(coset_scale_impl<P>(curve, 1, log_n, d, 0));
     ZK_HIP(hipMemcpy(out, d, n * eb, hipMemcpyDeviceToHost));
-    return ZK_OK;
-}
-
-template <class P>
-static int vec_op_host_impl(int op, uint64_t size, uint64_t n_a, const uint64_t* a, uint64_t n_b, const uint64_t* b, uint64_t* out) {
-    if (size == 0) return ZK_OK;
-    const size_t eb = P::W * 4;
-    DevBuf buf;
-    ZK_HIP_RC(buf.alloc(2 * size * eb));
-    uint32_t* const d = buf.as();
-    ZK_HIP(hipMemset(d, 0, 2 * size * eb));
-    uint64_t ca = n_a < size ? n_a : size, cb = n_b < size ? n_b : size;
-    if (ca) ZK_HIP(hipMemcpy(d, a, ca * eb, hipMemcpyHostToDevice));
-    if (cb) ZK_HIP(hipMemcpy(d + size * P::W, b, cb * eb, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((2 * size + 255) / 256)), dim3(256), 0, 0, 2 * size, d);
-    ZK_HIP_RC(vec_op_dev_impl<P>(op, size, d, d + size * P::W, d, 0));
-    ZK_HIP(hipMemcpy(out, d, size * eb, hipMemcpyDeviceToHost));
-    return ZK_OK;
-}
-
-template <class P>
-static int div_vanishing_host_impl(uint64_t n, uint64_t len, const uint64_t* coeffs, uint64_t* q, uint64_t* rem, int* rem_is_zero) {
-    if (n == 0) return fail(ZK_ERR_ARG, "vanishing polynomial of an empty domain");
-    *rem_is_zero = 1;
-    if (len == 0) return ZK_OK;
-    const size_t eb = P::W * 4;
-    uint64_t qlen = len > n ? len - n : 0, top = len < n ? len : n;
-    DevBuf dc, dq, dr, dflag;
-    ZK_HIP_RC(dc.alloc(len * eb));
-    ZK_HIP_RC(dq.alloc((qlen ? qlen : 1) * eb));
-    ZK_HIP_RC(dr.alloc(top * eb));
-    ZK_HIP_RC(dflag.alloc(sizeof(int)));
-    ZK_HIP(hipMemcpy(dc.as(), coeffs, len * eb, hipMemcpyHostToDevice));
-    (void)hipMemset(dflag.as(), 0, sizeof(int));
-    hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, 0, len, dc.as());
-    uint64_t lim = qlen > top ? qlen : top;
-    hipLaunchKernelGGL(div_vanishing_kernel<P>, dim3((unsigned)((lim + 255) / 256)), dim3(256), 0, 0, n, len, dc.as(), dq.as(), dr.as(), dflag.as<int>());
-    int flag = 0;
-    ZK_HIP(hipMemcpy(&flag, dflag.as(), sizeof(int), hipMemcpyDeviceToHost));
-    if (qlen) ZK_HIP(hipMemcpy(q, dq.as(), qlen * eb, hipMemcpyDeviceToHost));
-    ZK_HIP(hipMemcpy(rem, dr.as(), top * eb, hipMemcpyDeviceToHost));
-    *rem_is_zero = flag ? 0 : 1;
     return ZK_OK;
 }
 
@@ -720,15 +532,6 @@ static int div_vanishing_host_impl(uint64_t n, uint64_t len, const uint64_t* coe
 // u v is formed by the FIRST pass of the last inverse transform as it loads, and its LAST pass multiplies by -g^-i / (2N) and adds
 // w / 2: it writes h.  The quotient is exact iff a_i b_i = c_i on the domain itself, which is checked directly on the evaluation
 // vectors (the reference's "remainder must be zero", qap.py:68-69).
-struct QapTabs {
-    uint32_t *fwd = nullptr, *inv = nullptr;   // g^i / N and -g^-i R / (2N) as canonical Montgomery representatives, g = w_2n
-};
-static std::map<std::pair<int, int>, QapTabs> g_qap_tabs;   // (curve, log_n), under g_tw_mutex
-static void free_coset_tables() {  // caller holds g_tw_mutex
-    for (auto& kv : g_qap_tabs) { (void)hipFree(kv.second.fwd); (void)hipFree(kv.second.inv); }
-    g_qap_tabs.clear();
-}
-
 // row log_n of the stage-major twiddle tables holds w_2n^(+-i), i < n, as nine-word Montgomery representatives
 template <class P>
 __global__ void qap_tabs_kernel(uint32_t* __restrict__ fwd, uint32_t* __restrict__ inv, uint64_t n, const uint32_t* __restrict__ row_f,
@@ -742,27 +545,28 @@ __global__ void qap_tabs_kernel(uint32_t* __restrict__ fwd, uint32_t* __restrict
 template <class P>
 static int get_qap_tabs(int curve, int log_n, QapTabs* out, hipStream_t stream) {
     TwiddleSet ts;
-    int rc = get_twiddles<P>(curve, log_n + 1, &ts, stream);   // takes g_tw_mutex itself
+    int rc = get_twiddles<P>(curve, log_n + 1, &ts, stream);   // takes the owner's mutex itself: first this, then the lock
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(g_tw_mutex);
-    auto it = g_qap_tabs.find({curve, log_n});
-    if (it != g_qap_tabs.end()) { *out = it->second; return ZK_OK; }
+    std::lock_guard<std::mutex> lock(g_ntt.mutex);
+    auto it = g_ntt.qap_tabs.find({curve, log_n});
+    if (it != g_ntt.qap_tabs.end()) { *out = it->second; return ZK_OK; }
     const uint64_t n = 1ull << log_n;
-    QapTabs t;
-    ZK_HIP(hipMalloc(&t.fwd, n * P::W * 4));
-    hipError_t e_inv = hipMalloc(&t.inv, n * P::W * 4);
-    if (e_inv != hipSuccess) (void)hipFree(t.fwd);
-    ZK_HIP(e_inv);
+    TablePair tabs;
+    ZK_HIP_RC(tabs.alloc(n * P::W * 4));
     uint32_t nn[P::W] = {0};
     nn[0] = (uint32_t)n;
     const Fp<P> inv_n = fp_inv<P>(fp_from_canonical<P>(nn));                            // R / N
     const Fp<P> half = fp_inv<P>(fp_add<P>(fp_one<P>(), fp_one<P>()));                  // R / 2
     const Fp<P> c_inv = fp_mul<P>(fp_neg<P>(fp_mul<P>(inv_n, half)), fp_const<P>(P::R2));   // -(R / 2N) R^2 / R = -R^2 / (2N)
     const size_t row = (((size_t)1 << log_n) - 1) * TW_WORDS;
-    hipLaunchKernelGGL(qap_tabs_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t.fwd, t.inv, n, ts.fwd + row, ts.inv + row, inv_n, c_inv);
+    hipLaunchKernelGGL(qap_tabs_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tabs.a, tabs.b, n, ts.fwd + row, ts.inv + row, inv_n, c_inv);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipStreamSynchronize(stream));
-    g_qap_tabs[{curve, log_n}] = t;
+    QapTabs t;
+    t.fwd = tabs.a;
+    t.inv = tabs.b;
+    tabs.release();
+    g_ntt.qap_tabs[{curve, log_n}] = t;
     *out = t;
     return ZK_OK;
 }
@@ -778,26 +582,6 @@ __global__ void qap_eval_check_kernel(uint64_t n, const uint32_t* __restrict__ a
     one.v[0] = 1;
     Fp<P> r = fp_sub<P>(fp_mul<P>(load_fr<P>(a + i * P::W), load_fr<P>(b + i * P::W)), fp_mul<P>(load_fr<P>(c + i * P::W), one));
     if (!fp_is_zero<P>(r)) atomicOr(nonzero, 1);
-}
-
-static std::mutex g_uv_mutex;
-static std::map<hipStream_t, hipEvent_t> g_uv_events;  // one "u and v are final" event per stream (zk_qap_h_dev_begin)
-
-static int uv_event_for(hipStream_t stream, hipEvent_t* out) {
-    std::lock_guard<std::mutex> lock(g_uv_mutex);
-    auto it = g_uv_events.find(stream);
-    if (it == g_uv_events.end()) {
-        hipEvent_t e = nullptr;
-        ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        it = g_uv_events.emplace(stream, e).first;
-    }
-    *out = it->second;
-    return ZK_OK;
-}
-static void free_uv_events() {
-    std::lock_guard<std::mutex> lock(g_uv_mutex);
-    for (auto& kv : g_uv_events) (void)hipEventDestroy(kv.second);
-    g_uv_events.clear();
 }
 
 // divisible == nullptr: enqueue only (zk_qap_h_dev_begin); uv_ready (optional) is recorded once u and v are final
@@ -874,28 +658,8 @@ int zk_ntt(int curve, int inverse, int coset, uint64_t n_in, const uint64_t* in,
 #undef CALL
 }
 
-int zk_vec_op(int curve, int op, uint64_t size, uint64_t n_a, const uint64_t* a, uint64_t n_b, const uint64_t* b, uint64_t* out) {
-    if (op < 0 || op > 2) return fail(ZK_ERR_ARG, "unknown vector op");
-#define CALL(P) return vec_op_host_impl<P>(op, size, n_a, a, n_b, b, out)
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_poly_div_vanishing(int curve, uint64_t n, uint64_t len, const uint64_t* coeffs, uint64_t* q, uint64_t* rem, int* rem_is_zero) {
-#define CALL(P) return div_vanishing_host_impl<P>(n, len, coeffs, q, rem, rem_is_zero)
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
 int zk_ntt_dev(int curve, int inverse, int log_n, void* d_data, void* stream) {
 #define CALL(P) return ntt_dev_impl<P>(curve, inverse, log_n, (uint32_t*)d_data, (hipStream_t)stream)
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_op_dev(int curve, int op, uint64_t n, const void* d_a, const void* d_b, void* d_out, void* stream) {
-    if (op < 0 || op > 2) return fail(ZK_ERR_ARG, "unknown vector op");
-#define CALL(P) return vec_op_dev_impl<P>(op, n, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_out, (hipStream_t)stream)
     ZK_DISPATCH_FR(curve, CALL);
 #undef CALL
 }
@@ -909,7 +673,7 @@ int zk_qap_h_dev(int curve, int log_n, void* d_a_u, void* d_b_v, const void* d_c
 int zk_qap_h_dev_begin(int curve, int log_n, void* d_a_u, void* d_b_v, const void* d_c, void* d_h, void* d_work, void* stream, void** uv_ready) {
     hipEvent_t ev = nullptr;
     if (uv_ready) {
-        int rc = uv_event_for((hipStream_t)stream, &ev);
+        int rc = g_ntt.uv_event((hipStream_t)stream, &ev);
         if (rc) return rc;
         *uv_ready = (void*)ev;
     }
@@ -921,7 +685,7 @@ int zk_qap_h_dev_begin(int curve, int log_n, void* d_a_u, void* d_b_v, const voi
 int zk_qap_uv_dev(int curve, int log_n, void* d_a_u, void* d_b_v, void* stream, void** uv_ready) {
     hipEvent_t ev = nullptr;
     if (uv_ready) {
-        int rc = uv_event_for((hipStream_t)stream, &ev);
+        int rc = g_ntt.uv_event((hipStream_t)stream, &ev);
         if (rc) return rc;
         *uv_ready = (void*)ev;
     }
@@ -943,98 +707,8 @@ int zk_qap_h_dev_end(int curve, int log_n, const void* d_work, int* divisible, v
     return ZK_OK;
 }
 
-int zk_spmv_dev(int curve, uint64_t n_rows, const void* d_row_ptr, const void* d_cols, const void* d_vals,
-                const void* d_w, void* d_out, uint32_t skip_longer_than, void* stream) {
-    if (n_rows == 0) return ZK_OK;
-#define CALL(P)                                                                                                  \
-    {                                                                                                            \
-        hipLaunchKernelGGL(spmv_kernel<P>, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, \
-                           n_rows, (const uint32_t*)d_row_ptr, (const uint32_t*)d_cols, (const uint32_t*)d_vals,  \
-                           (const uint32_t*)d_w, (uint32_t*)d_out, skip_longer_than);                             \
-        ZK_HIP(hipGetLastError());                                                                               \
-        return ZK_OK;                                                                                            \
-    }
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_spmv_long_dev(int curve, uint64_t n_long, const void* d_long_rows, const void* d_item_ptr, uint64_t n_items,
-                     const void* d_items, const void* d_cols, const void* d_vals, const void* d_w, void* d_partials,
-                     void* d_out, void* stream) {
-    if (n_long == 0 || n_items == 0) return ZK_OK;
-#define CALL(P)                                                                                                          \
-    {                                                                                                                    \
-        hipLaunchKernelGGL(spmv_items_kernel<P>, dim3((unsigned)n_items), dim3(SPMV_LONG_THREADS), 0, (hipStream_t)stream, \
-                           (const uint32_t*)d_items, (const uint32_t*)d_cols, (const uint32_t*)d_vals,                   \
-                           (const uint32_t*)d_w, (uint32_t*)d_partials);                                                 \
-        hipLaunchKernelGGL(spmv_rows_kernel<P>, dim3((unsigned)n_long), dim3(SPMV_LONG_THREADS), 0, (hipStream_t)stream,   \
-                           (const uint32_t*)d_long_rows, (const uint32_t*)d_item_ptr, (const uint32_t*)d_partials,       \
-                           (uint32_t*)d_out);                                                                            \
-        ZK_HIP(hipGetLastError());                                                                                       \
-        return ZK_OK;                                                                                                    \
-    }
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_powers_dev(int curve, uint64_t n, const uint64_t* g, void* d_out, void* stream) {
-    if (n == 0) return ZK_OK;
-    if (n > (1ull << 32)) return fail(ZK_ERR_ARG, "too many powers");
-#define CALL(P)                                                                                                        \
-    {                                                                                                                  \
-        Fp<P> gm = fp_from_canonical<P>(reinterpret_cast<const uint32_t*>(g));                                         \
-        hipLaunchKernelGGL(powers_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,     \
-                           (uint32_t*)d_out, gm, (uint32_t)n);                                                         \
-        ZK_HIP(hipGetLastError());                                                                                     \
-        return ZK_OK;                                                                                                  \
-    }
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_canon_dev(int curve, uint64_t n, void* d_x, void* stream) {
-    if (n == 0) return ZK_OK;
-#define CALL(P)                                                                                                       \
-    {                                                                                                                 \
-        hipLaunchKernelGGL(canon_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,  \
-                           (uint32_t*)d_x);                                                                           \
-        ZK_HIP(hipGetLastError());                                                                                    \
-        return ZK_OK;                                                                                                 \
-    }
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-void zk_ntt_free_cache(void) {
-    free_twiddles();
-    free_scratch();
-}
-
-// zk_stream_destroy: the scratch vectors and the "u and v are final" event kept for this stream go with it (they used to stay
-// until zk_shutdown, and the next stream that was handed the same handle value inherited them).  The caller has
-// synchronised the stream: nothing queued on it reads the scratch any more.
-void zk_ntt_stream_released(void* stream) {
-    const hipStream_t st = (hipStream_t)stream;
-    uint32_t* ptr = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_scratch_mutex);
-        auto it = g_scratch.find(st);
-        if (it != g_scratch.end()) {
-            ptr = it->second.ptr;
-            g_scratch.erase(it);
-        }
-    }
-    if (ptr) (void)hipFree(ptr);
-    hipEvent_t ev = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_uv_mutex);
-        auto it = g_uv_events.find(st);
-        if (it != g_uv_events.end()) {
-            ev = it->second;
-            g_uv_events.erase(it);
-        }
-    }
-    if (ev) (void)hipEventDestroy(ev);
-}
+// the two hooks of host.hip (zk_shutdown, zk_stream_destroy)
+void zk_ntt_free_cache(void) { g_ntt.free_all(); }
+void zk_ntt_stream_released(void* stream) { g_ntt.release_stream((hipStream_t)stream); }
 
 }  // extern "C"

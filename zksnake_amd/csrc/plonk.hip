@@ -3,7 +3,8 @@
 // Stands in for the element-wise polynomial arithmetic of Plonk.prove in the reference
 // (python/zksnake/plonk/protocol.py:213-460: fft -> mul_over_evaluation_domain / add_over_evaluation_domain
 // chains, Polynomial scalar multiply-adds, Polynomial.__call__), fused so that one proof makes one pass over
-// each coset-evaluation vector.  SURVEY.md 8f row 2.
+// each coset-evaluation vector.  SURVEY.md 8f row 2.  What is PlonK's own or scan-based lives here; the generic
+// zk_vec_* operations the prover also calls (axpby, lincomb, gather, is_zero) are in frvec.hip.
 //
 // All vectors are canonical Fr elements (32 B) in HBM; scalars cross the ABI as canonical 4-limb integers.
 // Products use the Montgomery multiplier directly on canonical data: mont(x, s*R) = x*s, and chains of k
@@ -17,73 +18,6 @@
 
 namespace zkmi {
 using mem::DevBuf;
-
-template <class P>
-__host__ Fp<P> scalar_in(const uint64_t* s) {
-    return fp_unpack<P>(reinterpret_cast<const uint32_t*>(s));  // canonical integer as limbs
-}
-
-// s * R^k as an integer (k >= 0): what mont() must be fed to undo k divisions by R
-template <class P>
-__host__ Fp<P> scalar_times_r(const uint64_t* s, int k) {
-    Fp<P> v = scalar_in<P>(s);
-    for (int i = 0; i < k; ++i) v = fp_mul<P>(v, fp_const<P>(P::R2));
-    return fp_reduce_full<P>(v);
-}
-
-// out = a*x + b*y + c      (y may be null)
-template <class P>
-__global__ __launch_bounds__(256) void axpby_kernel(uint64_t n, Fp<P> a_m, const uint32_t* __restrict__ x, Fp<P> b_m,
-                                                    const uint32_t* __restrict__ y, Fp<P> c, uint32_t* __restrict__ out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fp<P> v = fp_add<P>(fp_mul<P>(load_fr<P>(x + i * P::W), a_m), c);
-    if (y) v = fp_add<P>(v, fp_mul<P>(load_fr<P>(y + i * P::W), b_m));
-    store_fr<P>(out + i * P::W, fp_reduce_full<P>(v));
-}
-
-// acc[i] += sum_k s_k x_k[i] (i < count_k), then acc[at_j] += c_j: a whole chain of scalar multiply-adds and single-coefficient
-// updates in ONE launch (the linearisation polynomial of a PlonK proof is ten such terms, a blinding two to three updates; as
-// separate launches of a few microseconds each they left the GPU idle between them: launch-bound)
-constexpr int LINCOMB_MAX_TERMS = 16, LINCOMB_MAX_AT = 8;
-template <class P>
-struct LincombArgs {
-    const uint32_t* x[LINCOMB_MAX_TERMS];
-    uint64_t count[LINCOMB_MAX_TERMS];
-    Fp<P> s_m[LINCOMB_MAX_TERMS];      // s R: mont(x, s R) = s x
-    uint64_t at[LINCOMB_MAX_AT];
-    Fp<P> at_val[LINCOMB_MAX_AT];      // canonical
-    int k, n_at;
-};
-template <class P>
-__global__ __launch_bounds__(256) void lincomb_kernel(uint64_t n, uint32_t* __restrict__ acc, LincombArgs<P> a) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fp<P> v = load_fr<P>(acc + i * P::W);
-    for (int t = 0; t < a.k; ++t)
-        if (i < a.count[t]) v = fp_add<P>(v, fp_mul<P>(load_fr<P>(a.x[t] + i * P::W), a.s_m[t]));
-    for (int j = 0; j < a.n_at; ++j)
-        if (i == a.at[j]) v = fp_add<P>(v, a.at_val[j]);
-    store_fr<P>(acc + i * P::W, fp_reduce_full<P>(fp_reduce_full<P>(v)));
-}
-
-// out[i] = in[offset + i * stride]: de-interleaves the flat PlonK witness [a0, b0, c0, a1, ..] into its three columns
-template <class P>
-__global__ __launch_bounds__(256) void gather_kernel(uint64_t n, const uint4* __restrict__ in, uint64_t stride, uint64_t offset, uint4* __restrict__ out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    constexpr int V = P::W / 4;  // 16-byte vectors per element
-    if (i >= n * V) return;
-    const uint64_t e = i / V, part = i % V;
-    out[i] = in[(offset + e * stride) * V + part];
-}
-
-template <class P>
-__global__ __launch_bounds__(256) void is_zero_kernel(uint64_t n_vec4, const uint4* __restrict__ x, int* flag) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_vec4) return;
-    uint4 t = x[i];
-    if (t.x | t.y | t.z | t.w) atomicOr(flag, 1);
-}
 
 // out[i] = prod_j (w_j[i] + beta * label_j[i] + gamma),  j = 0..2      (protocol.py:270-292 on the n-domain)
 template <class P>
@@ -347,63 +281,6 @@ static int div_linear_dev_impl(uint64_t n, const void* coeffs, const uint64_t* r
 // ---- host wrappers ------------------------------------------------------------------------------------
 
 template <class P>
-static int axpby_impl(uint64_t n, const uint64_t* a, const void* x, const uint64_t* b, const void* y, const uint64_t* c, void* out, hipStream_t st) {
-    if (n == 0) return ZK_OK;
-    if (!a || !x || !out) return fail(ZK_ERR_ARG, "axpby: null argument");
-    if ((b == nullptr) != (y == nullptr)) return fail(ZK_ERR_ARG, "axpby: b and y go together");
-    Fp<P> am = scalar_times_r<P>(a, 1), bm = b ? scalar_times_r<P>(b, 1) : fp_zero<P>(), cc = c ? scalar_in<P>(c) : fp_zero<P>();
-    hipLaunchKernelGGL(axpby_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, am, (const uint32_t*)x, bm,
-                       (const uint32_t*)y, cc, (uint32_t*)out);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
-}
-
-template <class P>
-static int lincomb_impl(uint64_t n_acc, void* acc, int k, const uint64_t* counts, const void* const* xs, const uint64_t* scalars, int n_at,
-                        const uint64_t* at_index, const uint64_t* at_vals, hipStream_t st) {
-    if (k < 0 || k > LINCOMB_MAX_TERMS || n_at < 0 || n_at > LINCOMB_MAX_AT) return fail(ZK_ERR_ARG, "lincomb: at most 16 terms and 8 single updates");
-    if (n_acc == 0 || (k == 0 && n_at == 0)) return ZK_OK;
-    if (!acc || (k && (!counts || !xs || !scalars)) || (n_at && (!at_index || !at_vals))) return fail(ZK_ERR_ARG, "lincomb: null argument");
-    LincombArgs<P> a;
-    a.k = k;
-    a.n_at = n_at;
-    uint64_t reach = 0;   // the launch only covers what some term or update touches
-    for (int t = 0; t < k; ++t) {
-        if (counts[t] > n_acc) return fail(ZK_ERR_ARG, "lincomb: a term is longer than the accumulator");
-        if (counts[t] && !xs[t]) return fail(ZK_ERR_ARG, "lincomb: null term");
-        a.x[t] = (const uint32_t*)xs[t];
-        a.count[t] = counts[t];
-        a.s_m[t] = scalar_times_r<P>(scalars + 4 * t, 1);
-        reach = std::max<uint64_t>(reach, counts[t]);
-    }
-    for (int j = 0; j < n_at; ++j) {
-        if (at_index[j] >= n_acc) return fail(ZK_ERR_ARG, "lincomb: update index beyond the accumulator");
-        a.at[j] = at_index[j];
-        a.at_val[j] = scalar_in<P>(at_vals + 4 * j);
-        reach = std::max<uint64_t>(reach, at_index[j] + 1);
-    }
-    hipLaunchKernelGGL(lincomb_kernel<P>, dim3((unsigned)((reach + 255) / 256)), dim3(256), 0, st, reach, (uint32_t*)acc, a);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
-}
-
-template <class P>
-static int is_zero_impl(uint64_t n, const void* x, int* is_zero, hipStream_t st) {
-    *is_zero = 1;
-    if (n == 0) return ZK_OK;
-    DevBuf dflag;
-    ZK_HIP_RC(dflag.alloc(sizeof(int)));
-    int flag = 0;
-    ZK_HIP(hipMemsetAsync(dflag.as(), 0, sizeof(int), st));
-    uint64_t nv = n * (P::W / 4);
-    hipLaunchKernelGGL(is_zero_kernel<P>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, nv, (const uint4*)x, dflag.as<int>());
-    ZK_HIP(hipMemcpyAsync(&flag, dflag.as(), sizeof(int), hipMemcpyDeviceToHost, st));
-    ZK_HIP(hipStreamSynchronize(st));
-    *is_zero = flag ? 0 : 1;
-    return ZK_OK;
-}
-
-template <class P>
 static int perm_terms_impl(uint64_t n, const void* const* w, const void* const* l, const uint64_t* beta, const uint64_t* gamma, void* out, hipStream_t st) {
     if (n == 0) return ZK_OK;
     hipLaunchKernelGGL(perm_terms_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const uint32_t*)w[0], (const uint32_t*)w[1],
@@ -498,40 +375,6 @@ extern "C" {
 int zk_poly_eval_many_dev(int curve, int k, const uint64_t* counts, const void* const* d_coeffs, const uint64_t* xs, uint64_t* outs, void* stream) {
     if (k < 0 || k > 64) return fail(ZK_ERR_ARG, "poly_eval_many: 0 .. 64 polynomials");
 #define CALL(P) return poly_eval_many_impl<P>(k, counts, d_coeffs, xs, outs, (hipStream_t)stream)
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_axpby_dev(int curve, uint64_t n, const uint64_t* a, const void* d_x, const uint64_t* b, const void* d_y, const uint64_t* c,
-                     void* d_out, void* stream) {
-#define CALL(P) return axpby_impl<P>(n, a, d_x, b, d_y, c, d_out, (hipStream_t)stream)
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_lincomb_dev(int curve, uint64_t n_acc, void* d_acc, int k, const uint64_t* counts, const void* const* d_x, const uint64_t* scalars,
-                       int n_at, const uint64_t* at_index, const uint64_t* at_vals, void* stream) {
-#define CALL(P) return lincomb_impl<P>(n_acc, d_acc, k, counts, d_x, scalars, n_at, at_index, at_vals, (hipStream_t)stream)
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_gather_dev(int curve, uint64_t n, const void* d_src, uint64_t stride, uint64_t offset, void* d_dst, void* stream) {
-#define CALL(P)                                                                                                            \
-    {                                                                                                                      \
-        if (n == 0) return ZK_OK;                                                                                          \
-        const uint64_t nv = n * (P::W / 4);                                                                                \
-        hipLaunchKernelGGL(gather_kernel<P>, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,     \
-                           (const uint4*)d_src, stride, offset, (uint4*)d_dst);                                            \
-        ZK_HIP(hipGetLastError());                                                                                         \
-        return ZK_OK;                                                                                                      \
-    }
-    ZK_DISPATCH_FR(curve, CALL);
-#undef CALL
-}
-
-int zk_vec_is_zero_dev(int curve, uint64_t n, const void* d_x, int* is_zero, void* stream) {
-#define CALL(P) return is_zero_impl<P>(n, d_x, is_zero, (hipStream_t)stream)
     ZK_DISPATCH_FR(curve, CALL);
 #undef CALL
 }
