@@ -506,6 +506,43 @@ int zk_rp_eval_dev(int curve, int log_bits, int log_N, const void* d_values, con
 int zk_rp_verify_scalars_dev(int curve, int log_bits, int log_N, const uint64_t* u, const uint64_t* u_inv, const uint64_t* a,
                              const uint64_t* b, const uint64_t* y_inv, const uint64_t* z, void* d_out, void* stream);
 
+/* ---- inner-product polynomial commitment, scalar side of an opening (csrc/pcs.hip) ----------------------------------------
+ * The halving argument of commitment/polynomial/ipa.py (BCMS20 appendix A) WITHOUT folding the generators and without a b
+ * vector.  It is not the argument of csrc/ipa.hip: one generator vector G, asymmetric folds c' = c_lo + u^-1 c_hi,
+ * G' = G_lo + u G_hi, b' = b_lo + u b_hi, and b = (1, z, z^2, ..) for the opening point z.  n = 2^log_n,
+ * 0 <= log_n <= ZK_PCS_MAX_LOG.  After k rounds with challenges u_0 .. u_(k-1), m = n >> k:
+ *   G^(k)_j = sum_{i = j mod m} s_i G_i,   s_i = prod_{t<k} (bit (log_n-1-t) of i ? u_t : 1),
+ *   b^(k)_j = B_k z^j,                     B_k = prod_{t<k} (1 + u_t z^(n >> (t+1)))   (one scalar, kept by the caller),
+ * so L_k and R_k are MSMs over the ORIGINAL G (n bases, one plan for a whole opening) with the scalars written here, plus the
+ * caller's B_k times an evaluation at z of half of c.  Vectors are canonical Fr elements in device memory; u, u_inv, z, c are
+ * canonical 4-limb integers in host memory, reduced on entry when >= r.  z^j is built per thread from the squarings z^(2^t),
+ * t <= 18, which travel as kernel arguments, and steps by z^(2^18) per grid-stride item.  Workgroups of 256 threads on a grid
+ * capped at 1024 workgroups: the pass over i < n takes a second item per thread first at n = 2^19, the fold (m items) and the
+ * evaluations (m/2 items) first at n = 2^20.  ZK_ERR_ARG for a null pointer, sizes out of range, an unknown curve, a challenge
+ * missing or present against the rules below, or two buffers that overlap; nothing is written then. */
+#define ZK_PCS_MAX_LOG 21
+/* Round k of an opening, 0 <= k <= log_n; m = n >> k, h = m / 2.  d_c: n elements, of which the first 2m are live on entry (n
+ * when k = 0) and the first m afterwards; d_s, d_scal_L, d_scal_R: n elements each.
+ * Step 1.  k = 0: u and u_inv must be NULL; s[i] = 1.  k >= 1: u, u_inv (4 limbs each) are the challenge of round k-1 and its
+ *   inverse (u * u_inv = 1 is not checked); in place for j < m
+ *     c[j] += u_inv c[j+m],
+ *   then for i < n with bit (log_n - k) of i set:  s[i] *= u.
+ * Step 2 (k < log_n only; z, 4 limbs, is the opening point), for i < n with j = i mod m:
+ *     j <  h:  scal_L[i] = c[j+h] s[i],  scal_R[i] = 0
+ *     j >= h:  scal_R[i] = c[j-h] s[i],  scal_L[i] = 0
+ *   (every element of d_scal_L, d_scal_R is written, zeros included), so that with h' the argument's second generator
+ *     L_k = <scal_L, G> + B_k evals[0..3] h',   R_k = <scal_R, G> + B_k z^h evals[4..7] h',
+ *     evals[0..3] = sum_{j<h} c[j+h] z^j,   evals[4..7] = sum_{j<h} c[j] z^j   (host, canonical; exact fixed-order sums).
+ * With k == log_n only step 1 runs: z, d_scal_L, d_scal_R and evals may be NULL and are not touched; c[0] is the proof's scalar.
+ * Synchronises the stream when it returns evals (k < log_n), otherwise it only enqueues. */
+int zk_pcs_round_dev(int curve, int log_n, int k, void* d_c, void* d_s, const uint64_t* u, const uint64_t* u_inv, const uint64_t* z,
+                     void* d_scal_L, void* d_scal_R, uint64_t* evals, void* stream);
+/* The verifier's scalars for the proof's c (4 limbs, host) and the challenges u (log_n * 4 limbs, host; may be NULL when
+ * log_n = 0): d_out[i] = c s_i for i < n with s_i as above for k = log_n -- the coefficients of the reference's
+ * g(X) = prod_i (1 + u_(log_n-1-i) X^(2^i)), times c -- n elements, at most log_n products per element.  log_n = 0 gives [c].
+ * Enqueues only. */
+int zk_pcs_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* c, void* d_out, void* stream);
+
 /* ---- GKR over layered circuits, the sparse side (csrc/gkr.hip) ----------------------------------------------------------
  * Layer j of a circuit has n_j wires and a dense table W_j of 2^k_j canonical Fr elements in device memory (zero beyond n_j),
  * 1 <= k_j <= ZK_GKR_MAX_LOG.  Gate g of layer j is (types[g]: 0 ADD / 1 MUL, in1[g], in2[g]) with in1, in2 < n_(j-1): three

@@ -9,32 +9,18 @@
 // Powers.  Every element needs y^k (or y^-k) and z^(2+j).  They are NOT read from tables: the squarings g^(2^t), t <= 18, travel
 // as kernel arguments, a thread builds the power of its first index from them (one product per set bit; bits 6 and up are the
 // same across a wave, so those branches are uniform) and steps by g^(2^18) per grid-stride item -- the stride is 2^18 whenever a
-// thread takes a second item, and it is a multiple of n, so z^(2+j) steps by a fixed power too.  2^i is the integer with bit i
-// set, written into its limb: no product.  DESIGN 4.10 has the count of products and bytes per element against the tables.
+// thread takes a second item, and it is a multiple of n, so z^(2+j) steps by a fixed power too (RpPowers / rp_power / rp_squarings,
+// fr_powers.hip.h, shared with pcs.hip).  2^i is the integer with bit i set, written into its limb: no product.  DESIGN 4.10 has
+// the count of products and bytes per element against the tables.
 //
 // Like ipa.hip the kernels keep data canonical and carry host scalars in Montgomery form: mont(x, s R) = x s.  A product of two
 // canonical values carries R^-1, which the sums close once per thread with R^2.
+#include "fr_powers.hip.h"
 #include "ipa_chain.hip.h"
 
 namespace zkmi {
 
 constexpr int RP_MAX_BITS_LOG = 7;           // bitsize <= 128: 2^i stays a plain integer below r
-constexpr int RP_SEED_BITS = 18;             // log2(FR_MAX_BLOCKS * MLE_TILE): a thread's first index has at most this many bits
-static_assert((1u << RP_SEED_BITS) == FR_MAX_BLOCKS * MLE_TILE, "the step of a power is the stride of the capped grid");
-
-// g^(2^t) R for t <= RP_SEED_BITS; the last one is the step of a grid-stride loop
-template <class P>
-struct RpPowers {
-    Fp<P> sq[RP_SEED_BITS + 1];
-};
-
-// acc g^e for e < 2^bits
-template <class P>
-__device__ __forceinline__ Fp<P> rp_power(const RpPowers<P>& g, uint64_t e, int bits, Fp<P> acc) {
-    for (int t = 0; t < bits; ++t)
-        if ((e >> t) & 1) acc = fp_mul<P>(acc, g.sq[t]);
-    return acc;
-}
 
 // the integer 2^i, i < 128, as limbs (no limb is indexed by a register: the selects keep the element in VGPRs)
 template <class P>
@@ -175,14 +161,6 @@ static int rp_check_sizes(const char* who, int log_bits, int log_n) {
     if (log_bits < 0 || log_bits > RP_MAX_BITS_LOG || log_n < log_bits || log_n > ZK_IPA_MAX_LOG)
         return fail(ZK_ERR_ARG, std::string(who) + ": need 0 <= log_bits <= 7 and log_bits <= log_N <= 22");
     return ZK_OK;
-}
-
-template <class P>
-static RpPowers<P> rp_squarings(const uint64_t* g) {
-    RpPowers<P> out;
-    out.sq[0] = fr_mont<P>(g);
-    for (int t = 1; t <= RP_SEED_BITS; ++t) out.sq[t] = fp_mul<P>(out.sq[t - 1], out.sq[t - 1]);
-    return out;
 }
 
 template <class P>

@@ -6,6 +6,7 @@ appear only for single field elements (challenges, evaluations), never per coeff
 """
 
 import ctypes
+import os
 
 import numpy as np
 
@@ -277,6 +278,50 @@ class FrOps:
         rem = np.zeros(4, dtype=np.uint64)
         N.check(N.load().zk_poly_div_linear_dev(self.cid, n, coeffs_ptr, N.u64p(self.one(root)), q_ptr, N.u64p(rem), None))
         return int.from_bytes(rem.tobytes(), "little")
+
+    def d_pcs_round(self, log_n, k, c_ptr, s_ptr, u=None, u_inv=None, z=None, scal_l_ptr=None, scal_r_ptr=None):
+        """round k of an inner-product polynomial commitment's opening (zk_pcs_round_dev): folds c and updates s with the
+        challenge of the round before (u, u_inv; None at k = 0), and for k < log_n writes the scalars of L_k, R_k and returns
+        (sum_{j<h} c[j+h] z^j, sum_{j<h} c[j] z^j); None at k = log_n"""
+        last = k == log_n
+        evals = np.zeros((2, 4), dtype=np.uint64)
+        N.check(N.load().zk_pcs_round_dev(self.cid, log_n, k, c_ptr, s_ptr, None if u is None else N.u64p(self.one(u)),
+                                          None if u_inv is None else N.u64p(self.one(u_inv)), None if z is None else N.u64p(self.one(z)),
+                                          scal_l_ptr, scal_r_ptr, None if last else N.u64p(evals), None))
+        return None if last else tuple(self.ints(evals))
+
+    def d_pcs_verify_scalars(self, log_n, us, c, out_ptr):
+        """out[i] = c * s_i for the challenges us (zk_pcs_verify_scalars_dev)"""
+        u_l = self.limbs([u % self.r for u in us]) if us else None
+        N.check(N.load().zk_pcs_verify_scalars_dev(self.cid, log_n, None if u_l is None else N.u64p(u_l), N.u64p(self.one(c)), out_ptr, None))
+
+    def random_vector(self, count):
+        """`count` scalars, exactly uniform below r, from the OS CSPRNG, as a (count, 4) limb array: 32-byte words masked to the
+        order's bit length, the words that are not below r drawn again (no Python integer per element)"""
+        r = self.r
+        r_limbs = [(r >> (64 * j)) & (2 ** 64 - 1) for j in range(4)]
+        top_mask = np.uint64((1 << (r.bit_length() - 192)) - 1)
+
+        def draw(k):
+            words = np.frombuffer(os.urandom(32 * k), dtype=np.uint64).reshape(k, 4).copy()
+            words[:, 3] &= top_mask
+            return words
+
+        def not_below_r(words):
+            below = np.zeros(words.shape[0], dtype=bool)
+            equal = np.ones(words.shape[0], dtype=bool)
+            for j in (3, 2, 1, 0):
+                limb = np.uint64(r_limbs[j])
+                below |= equal & (words[:, j] < limb)
+                equal &= words[:, j] == limb
+            return np.flatnonzero(~below)
+
+        out = draw(count)
+        bad = not_below_r(out)
+        while bad.size:
+            out[bad] = draw(bad.size)
+            bad = bad[not_below_r(out[bad])]
+        return out
 
     def d_perm_terms(self, n, wires, labels, beta, gamma, out_ptr):
         arr = ctypes.c_void_p * 3

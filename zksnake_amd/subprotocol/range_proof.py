@@ -34,7 +34,6 @@ argument, so no commitment is appended and no commitment MSM is run.
 """
 
 import hashlib
-import os
 import secrets
 import time
 
@@ -159,32 +158,8 @@ class RangeProof:
 
     # -- randomness --
     def random_vector(self, count):
-        """`count` scalars, exactly uniform below r, from the OS CSPRNG, as a (count, 4) limb array: 32-byte words masked to the
-        order's bit length, the words that are not below r drawn again (no Python integer per element)"""
-        r = self.E.order
-        r_limbs = [(r >> (64 * j)) & (2 ** 64 - 1) for j in range(4)]
-        top_mask = np.uint64((1 << (r.bit_length() - 192)) - 1)
-
-        def draw(k):
-            words = np.frombuffer(os.urandom(32 * k), dtype=np.uint64).reshape(k, 4).copy()
-            words[:, 3] &= top_mask
-            return words
-
-        def not_below_r(words):
-            below = np.zeros(words.shape[0], dtype=bool)
-            equal = np.ones(words.shape[0], dtype=bool)
-            for j in (3, 2, 1, 0):
-                limb = np.uint64(r_limbs[j])
-                below |= equal & (words[:, j] < limb)
-                equal &= words[:, j] == limb
-            return np.flatnonzero(~below)
-
-        out = draw(count)
-        bad = not_below_r(out)
-        while bad.size:
-            out[bad] = draw(bad.size)
-            bad = bad[not_below_r(out[bad])]
-        return out
+        """`count` scalars, exactly uniform below r, from the OS CSPRNG, as a (count, 4) limb array (FrOps.random_vector)"""
+        return self._ops.random_vector(count)
 
     def random(self):
         """the randomness of one proof, as `prove(.., randomness=)` takes it"""
