@@ -100,9 +100,9 @@ def main():
                 H = E.batch_mul(E.G1(), random_limbs(rng, n), as_array=True)
                 ipa, gens = InnerProductArgument(n, curve, generators=(G, H)), "batch_mul"
             t1 = time.perf_counter()
-            ipa._generator_bytes("G"), ipa._generator_bytes("H")
+            ipa._gens.bytes()
             t2 = time.perf_counter()
-            ipa._plan()
+            ipa._gens.bases().plan()
             N.load().zk_dev_synchronize()
             t3 = time.perf_counter()
             a, b = random_limbs(rng, n), random_limbs(rng, n)

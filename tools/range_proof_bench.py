@@ -119,7 +119,7 @@ def main():
             t1 = time.perf_counter()
             rp._generator_digest()
             t2 = time.perf_counter()
-            rp._ipa._plan()
+            rp._ipa._gens.bases().plan()
             N.load().zk_dev_synchronize()
             t3 = time.perf_counter()
             values = [int(v) for v in rng.integers(0, 1 << 63, size=m, dtype=np.uint64)] if args.bitsize >= 63 else \

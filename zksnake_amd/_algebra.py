@@ -20,6 +20,7 @@ limb arrays ((n, 4) uint64, canonical little-endian limbs) and `PointArray` obje
 2^20-element inputs do not pay Python big-int marshalling.
 """
 
+import ctypes
 import types
 
 import numpy as np
@@ -27,6 +28,7 @@ import numpy as np
 from . import _native as N
 from . import constant
 from . import pairing as _pairing
+from .frvec import DevVec
 
 _MODULUS = {0: constant.BN254_SCALAR_FIELD, 1: constant.BLS12_381_SCALAR_FIELD}
 _FIELD = {0: constant.BN254_MODULUS, 1: constant.BLS12_381_MODULUS}
@@ -165,6 +167,67 @@ class PointArray:
             if lib.zk_msm_plan_set_option(handle, b"priority_steps", 0) == N.ZK_OK:
                 self._plan_concurrent[handle] = True
         return handle
+
+    # -- MSMs on the plan --
+    @classmethod
+    def from_points(cls, curve_id, group, points, *, count=None, what="points"):
+        """`points` (a PointArray, returned as it is, or an iterable of points, packed row by row) as a PointArray of the given
+        curve and group: TypeError for anything else, ValueError unless it holds `count` points (None: any number)"""
+        if not isinstance(points, PointArray):
+            points = list(points)
+            if any(type(p) is not _point_class(curve_id, group) for p in points):
+                raise TypeError(f"{what} must be G{group} points of the expected curve")
+            points = cls(curve_id, group, _points_to_limbs(points, curve_id, group))
+        if points.curve_id != curve_id or points.group != group:
+            raise TypeError(f"{what} must be G{group} points of the expected curve")
+        if count is not None and len(points) != count:
+            raise ValueError(f"{count} {what} expected, got {len(points)}")
+        return points
+
+    def _point(self, limbs):
+        return _point_class(self.curve_id, self.group)._from_limbs(limbs)
+
+    def _scalars(self, scalars, count):
+        """(address, on_device flag, count, what keeps the address alive) for a DevVec, a device address or host limbs"""
+        if isinstance(scalars, int):
+            return scalars, 1, count, None
+        if isinstance(scalars, DevVec):
+            ptr, on_device, have = scalars.ptr(), 1, scalars.n
+        else:
+            scalars = _scalar_limbs(scalars, self.curve_id)
+            ptr, on_device, have = scalars.ctypes.data, 0, scalars.shape[0]
+        count = have if count is None else count
+        assert count <= have, "fewer scalars than the MSM reads"
+        return ptr, on_device, count, scalars
+
+    def msm(self, scalars, count=None, *, timings=None, **plan_options):
+        """<scalars[:count], self[:count]> on self.plan(**plan_options); count defaults to the number of scalars.  `scalars`: a
+        DevVec or a device address (read in place from HBM; an address needs `count`) or a host limb array.  No scalars give the
+        identity without a plan.  A list `timings` gets the milliseconds of the run (zk_msm_plan_timings, index 4) appended."""
+        ptr, on_device, count, _keep = self._scalars(scalars, count)
+        out = np.zeros(self.limbs.shape[1], dtype=np.uint64)
+        if count:
+            handle, lib = self.plan(**plan_options), N.load()
+            N.check(lib.zk_msm_plan_run(handle, count, ptr, on_device, 0, 0, N.u64p(out), None))
+            if timings is not None:
+                ms = (ctypes.c_float * 5)()
+                lib.zk_msm_plan_timings(handle, ms, 5)
+                timings.append(float(ms[4]))
+        return self._point(out)
+
+    def msm_enqueue(self, scalars, count=None, *, slot=0, **plan_options):
+        """start <scalars[:count], self[:count]> on the stream of the slot's plan and return at once: MSMs on different slots (or
+        arrays) run side by side.  `msm_finish` takes the handle returned here."""
+        ptr, on_device, count, keep = self._scalars(scalars, count)
+        handle = self.plan(slot=slot, **plan_options)
+        N.check(N.load().zk_msm_plan_enqueue(handle, count, ptr, on_device, 0, 0, N.STREAM_PLAN))
+        return handle, keep
+
+    def msm_finish(self, handle):
+        """wait for the MSM that `msm_enqueue` started: its point"""
+        out = np.zeros(self.limbs.shape[1], dtype=np.uint64)
+        N.check(N.load().zk_msm_plan_finish(handle[0], N.u64p(out)))
+        return self._point(out)
 
     def _drop(self, key):
         """destroy the plan of one (slot, mode); a run still in flight on it is cancelled first (waits for the plan's stream)"""
@@ -441,15 +504,14 @@ def _make_ec(cid):
         n_p = len(points)
         if n_s != n_p:
             raise ValueError("Number of points and scalars mismatch")
-        out = np.zeros(N.point_limbs(cid, group), dtype=np.uint64)
         if isinstance(points, PointArray) and n_p:
-            N.check(lib.zk_msm_plan_run(points.plan(), n_s, sc.ctypes.data, 0, 0, 0, N.u64p(out), None))
-        else:
-            base = _points_to_limbs(points, cid, group)
-            st = lib.zk_msm(cid, group, n_p, n_s, N.u64p(sc), N.u64p(base), N.u64p(out))
-            if st == N.ZK_ERR_LENGTH:
-                raise ValueError("Number of points and scalars mismatch")
-            N.check(st)
+            return points.msm(sc)
+        out = np.zeros(N.point_limbs(cid, group), dtype=np.uint64)
+        base = _points_to_limbs(points, cid, group)
+        st = lib.zk_msm(cid, group, n_p, n_s, N.u64p(sc), N.u64p(base), N.u64p(out))
+        if st == N.ZK_ERR_LENGTH:
+            raise ValueError("Number of points and scalars mismatch")
+        N.check(st)
         return _point_class(cid, group)._from_limbs(out)
 
     def multiscalar_mul_g1(points, scalars):

@@ -19,7 +19,6 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
-from ... import _native as N
 from ...constant import BLS12_381_SCALAR_FIELD, BN254_SCALAR_FIELD
 from ...ecc import ispointG1, ispointG2
 from ...frvec import DevVec, FrOps
@@ -44,10 +43,10 @@ def to_device(ops, polynomial):
         polynomial = polynomial.coeffs()
     if not isinstance(polynomial, (list, tuple, np.ndarray)):
         raise TypeError("a polynomial is a Polynomial, a list of ints, an (n, 4) limb array or a DevVec")
-    limbs = ops.limbs(polynomial)
-    vec = ops.d_from(limbs)
-    if isinstance(polynomial, np.ndarray) and limbs.shape[0]:
-        N.check(N.load().zk_vec_canon_dev(ops.cid, limbs.shape[0], vec.ptr(), None))
+    if isinstance(polynomial, np.ndarray):
+        polynomial = ops.limbs(polynomial)
+    vec = DevVec(len(polynomial), zero=False)
+    ops.d_load(vec, 0, polynomial, vec.n)
     return vec
 
 

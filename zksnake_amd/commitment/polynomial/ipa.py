@@ -26,12 +26,11 @@ G1 only, both curves, n = next_power_of_two(max_degree) <= 2^21.
 import secrets
 import time
 
-import numpy as np
-
 from ... import _native as N
-from ..._algebra import PointArray, _point_class
+from ..._algebra import PointArray
 from ...ecc import EllipticCurve
 from ...frvec import DevVec, FrOps
+from ...subprotocol._generators import GeneratorSet, round_profile
 from ...transcript import FiatShamirTranscript, hash_to_curve, hash_to_curve_limbs
 from ...utils import next_power_of_two
 from .base import MultiOpeningQuery, PolynomialCommitmentScheme
@@ -55,45 +54,16 @@ class IPA(PolynomialCommitmentScheme):
         self.E = EllipticCurve(self.group)
         self.order = self.E.order
         self._ops = FrOps(self.order)
-        self._G = self._H = None
-        self._bases = None
-        self._gen_bytes = None
-        self._hasher = None
+        self._gens = GeneratorSet(self.E, (self.n, None))    # G, H and the MSM plan over G || H (n + 1 bases in HBM)
         self.last_profile = None
 
     # -- generators --
-    def _changed(self):
-        self._gen_bytes = None
-        self._hasher = None
-        if self._bases is not None:
-            self._bases.release()
-            self._bases = None
-        self.is_setup = self._G is not None and self._H is not None
+    def _set(self, i, value):
+        self._gens.set(i, value)
+        self.is_setup = all(part is not None for part in self._gens.parts)
 
-    def _set_g(self, points):
-        if not isinstance(points, PointArray):
-            points = list(points)
-            limbs = np.zeros((len(points), N.point_limbs(self.E.curve_id, 1)), dtype=np.uint64)
-            for i, pt in enumerate(points):
-                if not isinstance(pt, self.E.curve.PointG1):
-                    raise TypeError("generators are G1 points of the scheme's curve")
-                limbs[i] = pt._limbs
-            points = PointArray(self.E.curve_id, 1, limbs)
-        if points.curve_id != self.E.curve_id or points.group != 1:
-            raise TypeError("generators are G1 points of the scheme's curve")
-        if len(points) != self.n:
-            raise ValueError(f"{self.n} generators expected, got {len(points)}")
-        self._G = points
-        self._changed()
-
-    def _set_h(self, point):
-        if not isinstance(point, self.E.curve.PointG1):
-            raise TypeError("H is a G1 point of the scheme's curve")
-        self._H = point
-        self._changed()
-
-    G = property(lambda self: self._G, _set_g)
-    H = property(lambda self: self._H, _set_h)
+    G = property(lambda self: self._gens.parts[0], lambda self, v: self._set(0, v))
+    H = property(lambda self: self._gens.parts[1], lambda self, v: self._set(1, v))
 
     def setup(self, seed=None):
         seed = seed or self.name.encode()
@@ -105,41 +75,7 @@ class IPA(PolynomialCommitmentScheme):
 
     def release(self):
         """free the MSM plan over G || H (it is rebuilt on the next use)"""
-        if self._bases is not None:
-            self._bases.release()
-            self._bases = None
-
-    # -- MSMs over G || H --
-    def _plan(self, slot=0):
-        """the MSM plan over G || H (n + 1 bases in HBM), created once per generator set; slot 1 is a clone over the same bases
-        with a workspace and a stream of its own, for the second MSM of a round"""
-        if self._bases is None:
-            self._bases = PointArray(self.E.curve_id, 1, np.concatenate([self._G.limbs, self._H._limbs.reshape(1, -1)]))
-        return self._bases.plan(slot=slot, concurrent=slot > 0)
-
-    def _msm(self, vec, count, timings=None):
-        """<vec[:count], G || H> for a device vector: count = n + 1 for a commitment, n for everything else"""
-        lib = N.load()
-        out = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
-        N.check(lib.zk_msm_plan_run(self._plan(), count, vec.ptr(), 1, 0, 0, N.u64p(out), None))
-        if timings is not None:
-            import ctypes
-            ms = (ctypes.c_float * 5)()
-            lib.zk_msm_plan_timings(self._plan(), ms, 5)
-            timings.append(float(ms[4]))
-        return _point_class(self.E.curve_id, 1)._from_limbs(out)
-
-    def _msm_pair(self, vec_l, vec_r):
-        """<vec_l, G> and <vec_r, G> in flight together, each on its plan's stream"""
-        lib, out = N.load(), []
-        handles = [self._plan(0), self._plan(1)]
-        for h, vec in zip(handles, (vec_l, vec_r)):
-            N.check(lib.zk_msm_plan_enqueue(h, self.n, vec.ptr(), 1, 0, 0, N.STREAM_PLAN))
-        for h in handles:
-            limbs = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
-            N.check(lib.zk_msm_plan_finish(h, N.u64p(limbs)))
-            out.append(_point_class(self.E.curve_id, 1)._from_limbs(limbs))
-        return out
+        self._gens.release()
 
     def _blinded(self, polynomial, blinding):
         """DevVec of n + 1 elements: the coefficients, zero padded to n, then the blinding"""
@@ -152,20 +88,8 @@ class IPA(PolynomialCommitmentScheme):
         return out
 
     def _transcript(self, transcript):
-        """the caller's transcript, or the default one, with every G_i and then H appended.  The default transcript always starts
-        with the same label and generators, so its hasher is kept after the first use and copied."""
-        if self._gen_bytes is None:
-            self._gen_bytes = self._G.to_bytes() + bytes(self._H.to_bytes())
-        if transcript is not None:
-            transcript.append(self._gen_bytes)
-            return transcript
-        transcript = FiatShamirTranscript(self.name.encode(), self.order)
-        if self._hasher is None:
-            transcript.append(self._gen_bytes)
-            self._hasher = transcript.hasher.copy()
-        else:
-            transcript.hasher = self._hasher.copy()
-        return transcript
+        """the caller's transcript, or the default one, with every G_i and then H appended"""
+        return self._gens.transcript(transcript, self.name.encode(), self.order)
 
     # -- randomness --
     def random(self, multi=False):
@@ -180,7 +104,7 @@ class IPA(PolynomialCommitmentScheme):
     def commit(self, polynomial, blinding: int):
         assert self.is_setup, "Trusted setup has not been run"
         N.ensure_gpu()
-        return self._msm(self._blinded(polynomial, blinding), self.n + 1)
+        return self._gens.msm(self._blinded(polynomial, blinding), self.n + 1)
 
     def open(self, polynomial, point, commitment, blinding, transcript=None, *, randomness=None, profile=False):
         """([L list, R list, C_bar, c, t'], evaluation)"""
@@ -199,7 +123,7 @@ class IPA(PolynomialCommitmentScheme):
         # a_bar: poly_r with its constant term lowered by poly_r(point), so that it vanishes at the point; then the blinding
         a_bar = self._blinded(randomness["poly_r"], randomness["t_bar"])
         ops.d_add_at(a_bar, 0, -ops.d_eval(n, a_bar.ptr(), point))
-        commitment_bar = self._msm(a_bar, n + 1)
+        commitment_bar = self._gens.msm(a_bar, n + 1)
         transcript.append(commitment_bar)
         alpha = transcript.get_challenge_scalar()
 
@@ -209,7 +133,7 @@ class IPA(PolynomialCommitmentScheme):
         N.check(N.load().zk_vec_axpby_dev(ops.cid, n, N.u64p(ops.one(1)), c.ptr(), N.u64p(ops.one(alpha)), a_bar.ptr(), None, c.ptr(), None))
         t_prime = (blinding + alpha * randomness["t_bar"]) % r
 
-        commitment_prime = self._msm(c, n)
+        commitment_prime = self._gens.msm(c, n)
         transcript.append(commitment_prime)
         h_prime = hash_to_curve(transcript.get_challenge(), b"U", self.E.name, 1)
         transcript.append(commitment_prime + h_prime * evaluation)
@@ -233,12 +157,7 @@ class IPA(PolynomialCommitmentScheme):
                 break
             hi, lo = ops.d_pcs_round(log_n, k, c.ptr(), s.ptr(), u, u_inv, z, scal_l.ptr(), scal_r.ptr())
             t1 = time.perf_counter()
-            if profile:      # one after the other, so that each run's stage timings can be read
-                msm_ms = []
-                L = self._msm(scal_l, n, msm_ms)
-                R = self._msm(scal_r, n, msm_ms)
-            else:
-                L, R = self._msm_pair(scal_l, scal_r)
+            L, R, msm_ms = self._gens.msm_lr(scal_l, scal_r, n, profile)
             t2 = time.perf_counter()
             z_h = pow(z, n >> (k + 1), r)
             L = L + h_prime * (b_scale * hi % r)
@@ -251,9 +170,7 @@ class IPA(PolynomialCommitmentScheme):
             u_inv = pow(u, -1, r)
             b_scale = b_scale * (1 + u * z_h) % r
             if profile:
-                t3 = time.perf_counter()
-                rounds.append({"round": k, "kernel_ms": (t1 - t0) * 1e3, "msm_wall_ms": (t2 - t1) * 1e3, "msm_ms": sum(msm_ms),
-                               "host_ms": (t3 - t2) * 1e3})
+                rounds.append(round_profile(k, t0, t1, t2, time.perf_counter(), msm_ms))
         if profile:
             self.last_profile = rounds
         return L_list, R_list, ops.ints(c.download(1, 0))[0]
@@ -278,7 +195,7 @@ class IPA(PolynomialCommitmentScheme):
         transcript.append(commitment)
         transcript.append(commitment_bar)
         alpha = transcript.get_challenge_scalar()
-        commitment_prime = commitment + commitment_bar * alpha - self._H * (t_prime % r)
+        commitment_prime = commitment + commitment_bar * alpha - self.H * (t_prime % r)
         transcript.append(commitment_prime)
         h_prime = hash_to_curve(transcript.get_challenge(), b"U", self.E.name, 1)
         C = commitment_prime + h_prime * (evaluation % r)
@@ -299,7 +216,7 @@ class IPA(PolynomialCommitmentScheme):
             z_pow = z_pow * z_pow % r
         scal = DevVec(n, zero=False)
         ops.d_pcs_verify_scalars(log_n, us, c, scal.ptr())
-        return C == self._msm(scal, n) + h_prime * (c * b % r)
+        return C == self._gens.msm(scal, n) + h_prime * (c * b % r)
 
     def multi_open(self, points_query: MultiOpeningQuery, transcript: FiatShamirTranscript = None, *, randomness=None):
         """(proof, the verifier's query).  proof = [commitment to f, q_1(x3), .., q_k(x3), opening of the final polynomial at x3]"""

@@ -6,10 +6,8 @@ the quotient, a multi-opening is two.  With the same tau, `commit` and `open` gi
 commitments, both curves.  base.py has the one deliberate difference of `multi_open` / `multi_verify` (a fixed group order).
 """
 
-import numpy as np
-
 from ... import _native as N
-from ..._algebra import PointArray, _point_class
+from ..._algebra import PointArray
 from ...ecc import EllipticCurve
 from ...frvec import DevVec, FrOps
 from ...transcript import FiatShamirTranscript
@@ -37,18 +35,7 @@ class KZG(PolynomialCommitmentScheme):
     # -- the SRS --
     def _set_g1(self, points):
         if points is not None:
-            if not isinstance(points, PointArray):
-                points = list(points)
-                limbs = np.zeros((len(points), N.point_limbs(self.E.curve_id, 1)), dtype=np.uint64)
-                for i, pt in enumerate(points):
-                    if not isinstance(pt, self.E.curve.PointG1):
-                        raise TypeError("the powers of tau are G1 points of the scheme's curve")
-                    limbs[i] = pt._limbs
-                points = PointArray(self.E.curve_id, 1, limbs)
-            if points.curve_id != self.E.curve_id or points.group != 1:
-                raise TypeError("the powers of tau are G1 points of the scheme's curve")
-            if len(points) != self.degree + 1:
-                raise ValueError(f"{self.degree + 1} powers of tau expected, got {len(points)}")
+            points = PointArray.from_points(self.E.curve_id, 1, points, count=self.degree + 1, what="powers of tau")
         if self._G1_tau is not None and self._G1_tau is not points:
             self._G1_tau.release()
         self._G1_tau = points
@@ -74,19 +61,11 @@ class KZG(PolynomialCommitmentScheme):
     def zero_commitment(self):
         return self.E.curve.PointG1.identity()
 
-    def _msm(self, vec, count):
-        """<vec[:count], G1_tau> for a device vector"""
-        if count == 0:
-            return self.zero_commitment()
-        out = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
-        N.check(N.load().zk_msm_plan_run(self._G1_tau.plan(), count, vec.ptr(), 1, 0, 0, N.u64p(out), None))
-        return _point_class(self.E.curve_id, 1)._from_limbs(out)
-
     def commit(self, polynomial):
         assert self.is_setup, "Trusted setup has not been run"
         N.ensure_gpu()
         vec = self._vec(polynomial, self.degree + 1)
-        return self._msm(vec, vec.n)
+        return self._G1_tau.msm(vec)
 
     def _open_vec(self, vec, count, point):
         """(proof, evaluation) for the first `count` coefficients of a device vector"""
@@ -94,7 +73,7 @@ class KZG(PolynomialCommitmentScheme):
             return self.zero_commitment(), 0
         quotient = DevVec(max(count - 1, 1), zero=False)
         evaluation = self._ops.d_div_linear(count, vec.ptr(), point % self.order, quotient.ptr())
-        return self._msm(quotient, count - 1), evaluation
+        return self._G1_tau.msm(quotient, count - 1), evaluation
 
     def open(self, polynomial, point):
         assert self.is_setup, "Trusted setup has not been run"
@@ -115,7 +94,7 @@ class KZG(PolynomialCommitmentScheme):
         N.ensure_gpu()
         transcript = transcript or FiatShamirTranscript(self.name.encode(), self.order)
         verifier_query, _, q_vecs, f, size, _ = self._multi_open_polys(points_query, transcript, self.degree + 1)
-        f_commitment = self._msm(f, size)
+        f_commitment = self._G1_tau.msm(f, size)
         transcript.append(f_commitment)
         x3 = transcript.get_challenge_scalar()
         q_x3, _ = self._multi_open_final(q_vecs, f, size, x3, transcript)

@@ -95,19 +95,9 @@ class EllipticCurve:
         if len(s) < len(g) and not isinstance(g, PointArray):
             g = g[: len(s)]
         if isinstance(g, PointArray) and len(s) < len(g):
-            return self._msm_prefix(g, s, group)
+            return g.msm(s)     # the first len(s) bases of a device-resident array (the plan ignores the tail)
         fn = self.curve.multiscalar_mul_g1 if group == 1 else self.curve.multiscalar_mul_g2
         return fn(g, s)
-
-    def _msm_prefix(self, g, s, group):
-        """first len(s) bases of a device-resident array (the plan ignores the tail)"""
-        import numpy as np
-        from . import _native as N
-        lib = N.ensure_gpu()
-        sc = _algebra._scalar_limbs(s, g.curve_id)
-        out = np.zeros(N.point_limbs(g.curve_id, group), dtype=np.uint64)
-        N.check(lib.zk_msm_plan_run(g.plan(), sc.shape[0], sc.ctypes.data, 0, 0, 0, N.u64p(out), None))
-        return _algebra._point_class(g.curve_id, group)._from_limbs(out)
 
     def from_hex(self, hexstring: str):
         data = bytes.fromhex(hexstring)

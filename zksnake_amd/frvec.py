@@ -195,6 +195,22 @@ class FrOps:
             vec.upload(limbs)
         return vec
 
+    def d_load(self, dst, offset, values, limit):
+        """values (a list of ints, an (n, 4) limb array -- canonicalised on the device -- or a DevVec, which is not modified; at
+        most `limit` elements) -> dst[offset:]; returns how many were written"""
+        limbs = None if isinstance(values, DevVec) else self.limbs(values)
+        n = values.n if limbs is None else limbs.shape[0]
+        if n > limit:
+            raise ValueError(f"at most {limit} elements")
+        assert offset + n <= dst.n
+        if n and limbs is None:
+            self.d_copy(n, values.ptr(), dst.ptr(offset))
+        elif n:
+            dst.upload(limbs, offset)
+            if isinstance(values, np.ndarray):
+                N.check(N.load().zk_vec_canon_dev(self.cid, n, dst.ptr(offset), None))
+        return n
+
     def d_powers(self, g, count):
         """DevVec of (1, g, g^2, ..), computed on the device"""
         vec = DevVec(count, zero=False)

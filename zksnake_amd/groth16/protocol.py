@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from .. import _native as N
+from .._algebra import _point_class
 from ..arithmetization.r1cs import R1CS
 from ..device import DeviceBuffer
 from ..ecc import EllipticCurve, PointArray
@@ -37,11 +38,7 @@ from .serialization import Proof, ProvingKey, VerifyingKey
 
 def _as_array(E, pts, group):
     """lists coming from ProvingKey.from_bytes become device-backed arrays on first use"""
-    if isinstance(pts, PointArray):
-        return pts
-    from .._algebra import _points_to_limbs
-    cid = E.curve.curve_id
-    return PointArray(cid, group, _points_to_limbs(pts, cid, group))
+    return PointArray.from_points(E.curve_id, group, pts, what="the key's points")
 
 
 def _ptr(buf):
@@ -328,7 +325,6 @@ class Groth16:
         return out
 
     def _points(self, parts):
-        from .._algebra import _point_class
         cid = self.E.curve.curve_id
         return [_point_class(cid, group)._from_limbs(t) for t, group in parts]
 

@@ -52,55 +52,37 @@ class Plonk:
         self.last_timings = {}
 
     # ------------------------------------------------------------------------------------------
-    def _tau_plan(self, slot=0):
-        """a resident fixed-base MSM plan over the proving key's tau_g1 (all commitments of a proof use these); slots are
-        independent workspaces, so the commitments of one round can be in flight together"""
-        pk, cid = self.proving_key, self.E.curve.curve_id
-        if not isinstance(pk.tau_g1, PointArray):
-            from .._algebra import _points_to_limbs
-            pk.tau_g1 = PointArray(cid, 1, _points_to_limbs(pk.tau_g1, cid, 1))
+    def _tau_g1(self, count=0):
+        """(the proving key's tau_g1 as a PointArray, the options of its resident fixed-base MSM plans): all commitments of a
+        proof use these; slots are independent workspaces, so the commitments of one round can be in flight together"""
+        pk = self.proving_key
+        assert count <= len(pk.tau_g1), "Constraints are too big for the given g1_tau"
+        pk.tau_g1 = PointArray.from_points(self.E.curve_id, 1, pk.tau_g1, what="powers of tau")
         # tau_g1 holds ~4n points but a commitment multiplies n + 2 .. 3n + 5 of them: below 2^20 gates the 16-bit windows
         # win (the wider windows the library would pick for the table's size pay only from ~2^20 scalars per MSM)
-        return pk.tau_g1.plan(slot, precompute=True, window_bits=16 if pk.n < (1 << 20) else 0, concurrent=True)
+        return pk.tau_g1, {"precompute": True, "window_bits": 16 if pk.n < (1 << 20) else 0, "concurrent": True}
 
     def _commit_many(self, jobs, meanwhile=None):
         """jobs: [(device vector, count, offset)] -> commitments; the MSMs of one round run concurrently on their plans'
         own streams (the latency-bound reduction of one hides behind the accumulation of the others).
         meanwhile: host work that does not need the results, done while the GPU runs them."""
-        lib, cid = N.load(), self.E.curve.curve_id
-        from .._algebra import _point_class
         handles = []
         for slot, (vec, count, offset) in enumerate(jobs):
-            assert count <= len(self.proving_key.tau_g1), "Constraints are too big for the given g1_tau"
-            h = self._tau_plan(slot)
-            N.check(lib.zk_msm_plan_enqueue(h, count, vec.ptr(offset), 1, 0, 0, N.STREAM_PLAN))
-            handles.append(h)
+            tau, options = self._tau_g1(count)
+            handles.append(tau.msm_enqueue(vec.ptr(offset), count, slot=slot, **options))
         if meanwhile is not None:
             meanwhile()
-        points = []
-        for h in handles:
-            out = np.zeros(N.point_limbs(cid, 1), dtype=np.uint64)
-            N.check(lib.zk_msm_plan_finish(h, N.u64p(out)))
-            points.append(_point_class(cid, 1)._from_limbs(out))
-        return points
-
-    def _run_plan(self, count, scalars_ptr, on_device):
-        cid = self.E.curve.curve_id
-        assert count <= len(self.proving_key.tau_g1), "Constraints are too big for the given g1_tau"
-        out = np.zeros(N.point_limbs(cid, 1), dtype=np.uint64)
-        if count:
-            N.check(N.load().zk_msm_plan_run(self._tau_plan(), count, scalars_ptr, on_device, 0, 0, N.u64p(out), None))
-        from .._algebra import _point_class
-        return _point_class(cid, 1)._from_limbs(out)
+        return [tau.msm_finish(h) for h in handles]
 
     def _commit(self, coeffs):
         """<tau_g1[:len], coeffs> for a coefficient vector in host memory"""
-        coeffs = np.ascontiguousarray(coeffs)
-        return self._run_plan(coeffs.shape[0], coeffs.ctypes.data, 0)
+        tau, options = self._tau_g1(len(coeffs))
+        return tau.msm(coeffs, **options)
 
     def _commit_dev(self, vec, count, offset=0):
         """<tau_g1[:count], vec[offset:offset+count]> with the scalars read in place from HBM"""
-        return self._run_plan(count, vec.ptr(offset), 1)
+        tau, options = self._tau_g1(count)
+        return tau.msm(vec.ptr(offset), count, **options)
 
     def setup(self, g1_tau=None, g2_tau=None, prepare_prover=True):
         """universal setup (or reuse of given powers of tau) + circuit preprocessing (protocol.py:39-155).
@@ -138,8 +120,9 @@ class Plonk:
         self.verifying_key = VerifyingKey(n, self.G2_tau, pk.tau_selector_poly, pk.tau_permutation_poly, self.E.name)
         if prepare_prover:
             self._key_columns()
+            tau, options = self._tau_g1()
             for slot in range(1, 3):   # a round commits to at most three polynomials at once
-                self._tau_plan(slot)
+                tau.plan(slot, **options)
 
     # ------------------------------------------------------------------------------------------
     def _quotient_domain(self):

@@ -19,18 +19,18 @@ Two differences from the reference, both deliberate:
 G1 only, both curves, n <= 2^21 (2n bases fit the largest split-scalar MSM plan).
 """
 
-import ctypes
 import time
 
 import numpy as np
 
 from .. import _native as N
-from .._algebra import PointArray, _point_class
+from .._algebra import PointArray
 from ..ecc import CurvePointSize, EllipticCurve
 from ..frvec import DevVec, FrOps
 from ..mle import sumcheck_round
-from ..transcript import FiatShamirTranscript, hash_to_curve, hash_to_curve_limbs
+from ..transcript import hash_to_curve, hash_to_curve_limbs
 from ..utils import next_power_of_two, split_list
+from ._generators import GeneratorSet, round_profile
 
 MAX_LOG = 21
 
@@ -81,9 +81,7 @@ class InnerProductArgument:
             raise ValueError(f"the inner-product argument takes at most 2^{MAX_LOG} elements")
         self.E = EllipticCurve(curve)
         self._ops = FrOps(self.E.order)
-        self._bases = None
-        self._bytes = {}
-        self._hasher = None
+        self._gens = GeneratorSet(self.E, (self.n, self.n))    # G, H and the MSM plan over G || H (2n bases in HBM)
         if generators is not None:
             self.G, self.H = generators
         else:
@@ -92,102 +90,12 @@ class InnerProductArgument:
         self.Q = Q
         self.last_profile = None
 
-    # -- generators --
-    def _as_array(self, points):
-        if not isinstance(points, PointArray):
-            points = list(points)
-            limbs = np.zeros((len(points), N.point_limbs(self.E.curve_id, 1)), dtype=np.uint64)
-            for i, pt in enumerate(points):
-                if not isinstance(pt, self.E.curve.PointG1):
-                    raise TypeError("generators are G1 points of the argument's curve")
-                limbs[i] = pt._limbs
-            points = PointArray(self.E.curve_id, 1, limbs)
-        if points.curve_id != self.E.curve_id or points.group != 1:
-            raise TypeError("generators are G1 points of the argument's curve")
-        if len(points) != self.n:
-            raise ValueError(f"{self.n} generators expected, got {len(points)}")
-        return points
-
-    def _set(self, name, points):
-        self.__dict__["_" + name] = self._as_array(points)
-        self._bytes.pop(name, None)
-        self._hasher = None
-        if self._bases is not None:
-            self._bases.release()
-            self._bases = None
-
-    G = property(lambda self: self._G, lambda self, v: self._set("G", v))
-    H = property(lambda self: self._H, lambda self, v: self._set("H", v))
-
-    def _generator_bytes(self, name):
-        """every point's compressed encoding, back to back: what appending the points one by one adds to the transcript"""
-        if name not in self._bytes:
-            self._bytes[name] = getattr(self, name).to_bytes()
-        return self._bytes[name]
-
-    def _plan(self, slot=0):
-        """the MSM plan over G || H (2n bases in HBM), created once per generator set; slot 1 is a clone over the same bases
-        with a workspace and a stream of its own, for the second MSM of a round"""
-        if self._bases is None:
-            self._bases = PointArray(self.E.curve_id, 1, np.concatenate([self._G.limbs, self._H.limbs]))
-        return self._bases.plan(slot=slot, concurrent=slot > 0)
-
-    def _msm(self, vec, timings=None):
-        """<vec, G || H> for a device vector of 2n scalars"""
-        lib = N.load()
-        out = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
-        N.check(lib.zk_msm_plan_run(self._plan(), 2 * self.n, vec.ptr(), 1, 0, 0, N.u64p(out), None))
-        if timings is not None:
-            ms = (ctypes.c_float * 5)()
-            lib.zk_msm_plan_timings(self._plan(), ms, 5)
-            timings.append(float(ms[4]))
-        return _point_class(self.E.curve_id, 1)._from_limbs(out)
-
-    def _msm_pair(self, vec_l, vec_r):
-        """<vec_l, G || H> and <vec_r, G || H> in flight together, each on its plan's stream"""
-        lib, out = N.load(), []
-        handles = [self._plan(0), self._plan(1)]
-        for h, vec in zip(handles, (vec_l, vec_r)):
-            N.check(lib.zk_msm_plan_enqueue(h, 2 * self.n, vec.ptr(), 1, 0, 0, N.STREAM_PLAN))
-        for h in handles:
-            limbs = np.zeros(N.point_limbs(self.E.curve_id, 1), dtype=np.uint64)
-            N.check(lib.zk_msm_plan_finish(h, N.u64p(limbs)))
-            out.append(_point_class(self.E.curve_id, 1)._from_limbs(limbs))
-        return out
-
-    def _load(self, dst, offset, values):
-        """values (list of ints, limb array or DevVec; at most n elements) -> dst[offset : offset + n], zero padded"""
-        ops, n = self._ops, self.n
-        if isinstance(values, DevVec):
-            if values.n > n:
-                raise ValueError(f"at most {n} elements")
-            if values.n:
-                ops.d_copy(values.n, values.ptr(), dst.ptr(offset))
-            return
-        limbs = ops.limbs(values)
-        if limbs.shape[0] > n:
-            raise ValueError(f"at most {n} elements")
-        if limbs.shape[0]:
-            dst.upload(limbs, offset)
-            if isinstance(values, np.ndarray):
-                N.check(N.load().zk_vec_canon_dev(ops.cid, limbs.shape[0], dst.ptr(offset), None))
+    G = property(lambda self: self._gens.parts[0], lambda self, v: self._gens.set(0, v))
+    H = property(lambda self: self._gens.parts[1], lambda self, v: self._gens.set(1, v))
 
     def _transcript(self, transcript):
-        """the caller's transcript, or the default one, with every G_i and then every H_i appended.  The default transcript
-        always starts with the same label and generators (64 MiB of them at n = 2^20), so its hasher is kept after the first
-        use and copied."""
-        if transcript is not None:
-            transcript.append(self._generator_bytes("G"))
-            transcript.append(self._generator_bytes("H"))
-            return transcript
-        transcript = FiatShamirTranscript(self.n.to_bytes(32, "big"), field=self.E.order)
-        if self._hasher is None:
-            transcript.append(self._generator_bytes("G"))
-            transcript.append(self._generator_bytes("H"))
-            self._hasher = transcript.hasher.copy()
-        else:
-            transcript.hasher = self._hasher.copy()
-        return transcript
+        """the caller's transcript, or the default one, with every G_i and then every H_i appended"""
+        return self._gens.transcript(transcript, self.n.to_bytes(32, "big"), self.E.order)
 
     def prove(self, a, b, transcript=None, profile=False):
         """(InnerProductProof, commitment, <a, b>).  a, b: lists of ints, (k, 4) limb arrays or DevVecs of at most n elements
@@ -197,10 +105,10 @@ class InnerProductArgument:
         transcript = self._transcript(transcript)
 
         ab_vec = DevVec(2 * n)                       # a || b: the commitment's scalars, then folded in place
-        self._load(ab_vec, 0, a)
-        self._load(ab_vec, n, b)
+        ops.d_load(ab_vec, 0, a, n)
+        ops.d_load(ab_vec, n, b, n)
         ab = sum(sumcheck_round(ops, log_n, [ab_vec.ptr(0), ab_vec.ptr(n)], [(1, (0, 1))])[:2 if log_n else 1]) % r
-        commitment = self._msm(ab_vec)
+        commitment = self._gens.msm(ab_vec, 2 * n)
         if self.Q is not None:
             Q = self.Q
         else:
@@ -233,12 +141,7 @@ class InnerProductArgument:
             if last:
                 break
             t1 = time.perf_counter()
-            if profile:      # one after the other, so that each run's stage timings can be read
-                msm_ms = []
-                L = self._msm(scal_l, msm_ms)
-                R = self._msm(scal_r, msm_ms)
-            else:
-                L, R = self._msm_pair(scal_l, scal_r)
+            L, R, msm_ms = self._gens.msm_lr(scal_l, scal_r, 2 * n, profile)
             t2 = time.perf_counter()
             c = ops.ints(cross)
             L = L + Q * c[0]
@@ -250,9 +153,7 @@ class InnerProductArgument:
             challenge = transcript.get_challenge_scalar()
             u, u_inv = ops.one(challenge), ops.one(pow(challenge, -1, r))
             if profile:
-                t3 = time.perf_counter()
-                rounds.append({"round": k, "kernel_ms": (t1 - t0) * 1e3, "msm_wall_ms": (t2 - t1) * 1e3, "msm_ms": sum(msm_ms),
-                               "host_ms": (t3 - t2) * 1e3})
+                rounds.append(round_profile(k, t0, t1, t2, time.perf_counter(), msm_ms))
         final = ops.ints(ab_vec.download(1, 0)) + ops.ints(ab_vec.download(1, n))
         if profile:
             self.last_profile = rounds
@@ -285,14 +186,12 @@ class InnerProductArgument:
         N.check(lib.zk_ipa_verify_scalars_dev(ops.cid, log_n, None if u_l is None else N.u64p(u_l), None if ui_l is None else N.u64p(ui_l),
                                               N.u64p(ops.one(proof.a)), N.u64p(ops.one(proof.b)), scal.ptr(), None))
         lhs = commitment + Q * (inner_product_result % r)
-        rhs = self._msm(scal) + Q * (proof.a * proof.b % r) - sum_LR
+        rhs = self._gens.msm(scal, 2 * n) + Q * (proof.a * proof.b % r) - sum_LR
         return lhs == rhs
 
     def release(self):
         """free the MSM plan over G || H (it is rebuilt on the next use)"""
-        if self._bases is not None:
-            self._bases.release()
-            self._bases = None
+        self._gens.release()
 
 
 __all__ = ["InnerProductArgument", "InnerProductProof"]

@@ -238,7 +238,7 @@ class RangeProof:
             given = rnd[key]
             if (given.n if isinstance(given, DevVec) else len(given)) != size:
                 raise ValueError(f"{key} must have {size} elements")
-            ipa._load(s_vec, offset, given)
+            ops.d_load(s_vec, offset, given, size)
         bits_vec = DevVec(2 * size, zero=False)   # a_L || a_R: the scalars of A
         if profile:
             N.check(lib.zk_dev_synchronize())
@@ -249,7 +249,7 @@ class RangeProof:
         t_load = clock()
         V = self._commit_values(values, gamma)
         t_commit = clock()
-        A, S = ipa._msm_pair(bits_vec, s_vec)
+        A, S, _ = ipa._gens.msm_lr(bits_vec, s_vec, 2 * size)
         A = A + self.B_blinding * alpha
         S = S + self.B_blinding * rho
         t_pair = clock()
@@ -345,7 +345,7 @@ class RangeProof:
         N.check(lib.zk_rp_verify_scalars_dev(ops.cid, lb, ln, None if u_l is None else N.u64p(u_l), None if ui_l is None else N.u64p(ui_l),
                                              N.u64p(ops.one(ip.a)), N.u64p(ops.one(ip.b)), N.u64p(ops.one(pow(y, -1, r))), N.u64p(ops.one(z)),
                                              scal.ptr(), None))
-        check = ipa._msm(scal)
+        check = ipa._gens.msm(scal, 2 * size)
         v_scalars = [c * wj % r for wj in self._weights(z)]
         if m < BATCH_MIN:
             for p, s in zip(V, v_scalars):
