@@ -543,6 +543,36 @@ int zk_pcs_round_dev(int curve, int log_n, int k, void* d_c, void* d_s, const ui
  * Enqueues only. */
 int zk_pcs_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* c, void* d_out, void* stream);
 
+/* ---- Merkle vector commitment: BLAKE2b leaves, tree and opening paths (csrc/merkle.hip) ----------------------------------
+ * The hashing of commitment/vector/merkle.py with alg = "blake2b": BLAKE2b-512 without key, salt or personalisation (RFC 7693,
+ * what hashlib.new("blake2b", data) computes), one digest per lane.  A tree over n leaves is its levels one after the other in
+ * device memory, ZK_MERKLE_DIGEST bytes per node: level 0 (the n leaf digests) first, level l has ceil(n_(l-1) / 2) nodes, the
+ * root is the last node; depth = ceil(log2 n), and n = 1 is depth 0 with the root equal to the leaf digest.  Parent i of a level
+ * is H(child[2i] || child[2i+1]), with child[2i] in the place of a right sibling that does not exist (the reference's
+ * _build_tree).  Workgroups of 256 threads on a grid capped at 1024 workgroups: a pass takes a second item per thread first
+ * past 2^18 items.  Digests, trees and paths start at a multiple of 16 bytes, offsets and indices at a multiple of 8.
+ * ZK_ERR_ARG, before anything is launched, for n = 0 or n > 2^ZK_MERKLE_MAX_LOG, a null pointer (d_rows / d_data may be NULL
+ * when there are no bytes to read), a misaligned one, row_bytes >= 2^32 or an output that overlaps an input.  No entry point
+ * allocates device memory; all of them only enqueue on `stream`. */
+#define ZK_MERKLE_DIGEST 64
+#define ZK_MERKLE_MAX_LOG 26     /* at most 2^26 leaves, the MSM plans' point limit: 4 GiB of leaf digests, < 8 GiB of tree */
+/* d_digests[i] = BLAKE2b(the row_bytes bytes at d_rows + i * row_bytes), i < n.  64-bit loads when d_rows and row_bytes are
+ * multiples of 8, byte loads otherwise; row_bytes = 0 gives n digests of the empty message. */
+int zk_blake2b_rows_dev(uint64_t n, const void* d_rows, uint64_t row_bytes, void* d_digests, void* stream);
+/* The same over items of any lengths: item i is bytes [off[i], off[i+1]) of d_data (data_bytes bytes), d_offsets: n + 1 uint64
+ * in device memory.  The kernel clamps end = min(off[i+1], data_bytes), start = min(off[i], end): offsets that are out of range
+ * or out of order give the digests of the clamped ranges and never a read outside d_data. */
+int zk_blake2b_items_dev(uint64_t n, const void* d_data, uint64_t data_bytes, const void* d_offsets, void* d_digests, void* stream);
+/* Host arithmetic only (works without a GPU): depth, the first node of every level (depth + 1 entries, room for
+ * ZK_MERKLE_MAX_LOG + 1) and the number of nodes.  Each output may be NULL. */
+int zk_merkle_layout(uint64_t n, int* depth, uint64_t* level_offset /* ZK_MERKLE_MAX_LOG + 1 entries, in nodes */, uint64_t* nodes);
+/* Levels 1 .. depth of d_tree (`nodes` nodes) from level 0, which the caller has put at its front; level 0 is not written. */
+int zk_merkle_build_dev(uint64_t n, void* d_tree, void* stream);      /* level 0 already in place at the front of d_tree */
+/* d_paths: k * depth nodes; entry (q, l) is the sibling of the level-l ancestor of leaf d_indices[q]: node idx ^ 1 of that level,
+ * or node idx itself where idx ^ 1 is past the level (the copy its parent was hashed from), so that the reference's verify loop
+ * accepts every path.  An index >= n opens leaf n - 1.  One gather; k = 0 is ZK_OK and launches nothing, as is depth = 0. */
+int zk_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices /* k uint64 */, void* d_paths, void* stream);
+
 /* ---- GKR over layered circuits, the sparse side (csrc/gkr.hip) ----------------------------------------------------------
  * Layer j of a circuit has n_j wires and a dense table W_j of 2^k_j canonical Fr elements in device memory (zero beyond n_j),
  * 1 <= k_j <= ZK_GKR_MAX_LOG.  Gate g of layer j is (types[g]: 0 ADD / 1 MUL, in1[g], in2[g]) with in1, in2 < n_(j-1): three

@@ -41,6 +41,8 @@ MSM_ROUTES_TWO_LEVEL = (MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MS
 IPA_MAX_LOG = 22  # ZK_IPA_MAX_LOG: an inner-product argument has at most 2^22 elements per vector
 PCS_MAX_LOG = 21  # ZK_PCS_MAX_LOG: an inner-product polynomial commitment has at most 2^21 coefficients
 MLE_TILE_LOG = 8  # ZK_MLE_TILE_LOG: variables one launch of the multilinear kernels folds per 256-element tile
+MERKLE_DIGEST = 64  # ZK_MERKLE_DIGEST: bytes per BLAKE2b-512 digest, and per node of a Merkle tree
+MERKLE_MAX_LOG = 26  # ZK_MERKLE_MAX_LOG: a Merkle tree has at most 2^26 leaves
 GKR_MAX_LOG = 24  # ZK_GKR_MAX_LOG: a layer of a GKR circuit has at most 2^24 wires
 GKR_LONG_ROW = 64  # ZK_GKR_LONG_ROW: CSR rows with more entries leave the lane-per-row kernel of the GKR passes
 
@@ -146,6 +148,11 @@ SIGNATURES = {
     "zk_rp_verify_scalars_dev": (_i, [_i, _i, _i, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
     "zk_pcs_round_dev": (_i, [_i, _i, _i, _vp, _vp, _u64p, _u64p, _u64p, _vp, _vp, _u64p, _vp]),
     "zk_pcs_verify_scalars_dev": (_i, [_i, _i, _u64p, _u64p, _vp, _vp]),
+    "zk_blake2b_rows_dev": (_i, [_u64, _vp, _u64, _vp, _vp]),
+    "zk_blake2b_items_dev": (_i, [_u64, _vp, _u64, _vp, _vp, _vp]),
+    "zk_merkle_layout": (_i, [_u64, ctypes.POINTER(_i), _u64p, _u64p]),
+    "zk_merkle_build_dev": (_i, [_u64, _vp, _vp]),
+    "zk_merkle_paths_dev": (_i, [_u64, _vp, _u64, _vp, _vp, _vp]),
     "zk_gkr_layer_eval_dev": (_i, [_i, _u64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "zk_gkr_eq_table_dev": (_i, [_i, _i, _u64p, _vp, _vp]),
     "zk_gkr_phase1_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1,2 +1,2 @@
-"""Commitment schemes (the reference's `zksnake.commitment`): polynomial commitments on the GPU.  The vector commitment (`Merkle`)
-is not part of this package: its hot path is a blake2b kernel."""
+"""Commitment schemes (the reference's `zksnake.commitment`): polynomial commitments (`commitment.polynomial`: KZG, IPA, multi-point
+openings) and the vector commitment (`commitment.vector`: a BLAKE2b Merkle tree; section 4.12), on the GPU."""
