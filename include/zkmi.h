@@ -573,6 +573,43 @@ int zk_merkle_build_dev(uint64_t n, void* d_tree, void* stream);      /* level 0
  * accepts every path.  An index >= n opens leaf n - 1.  One gather; k = 0 is ZK_OK and launches nothing, as is depth = 0. */
 int zk_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices /* k uint64 */, void* d_paths, void* stream);
 
+/* ---- FRI polynomial commitment: low-degree extension, fold and row gather (csrc/fri.hip) ------------------------------------
+ * The device side of commitment/polynomial/fri.py (the reference has no FRI).  A layer f of M = 2h canonical Fr elements on a
+ * coset s <w> (w of order M) is stored in PAIR ORDER: g[2j] = f[j], g[2j+1] = f[j+h] for j < h, the values at x_j = s w^j and at
+ * -x_j, so that leaf j of the layer's Merkle tree is the 64 bytes at g + 64 j (zk_blake2b_rows_dev(h, g, 64, ..)).  A layer of
+ * one element is that element.  Vectors are canonical Fr elements in device memory and start at a multiple of 16 bytes;
+ * scalars are canonical 4-limb integers in host memory, reduced on entry when >= r.  Powers are built per thread from the
+ * squarings of the scalar, t <= 18, which travel as kernel arguments, and step by its 2^18-th squaring per grid-stride item.
+ * Workgroups of 256 threads on a grid capped at 1024 workgroups.  ZK_ERR_ARG, before anything is launched or written, for a
+ * null or misaligned pointer, a size out of range, an unknown curve or two buffers of a call that overlap.  All three entry
+ * points only enqueue on `stream`, and none allocates device memory (zk_ntt_dev, which zk_fri_lde_dev calls, keeps its twiddle
+ * tables in the transform's own cache). */
+#define ZK_FRI_MAX_LOG 26            /* a layer has at most 2^26 elements: the domain of the largest polynomial times its blowup */
+#define ZK_FRI_MAX_ROW_BYTES 65536   /* zk_fri_rows_dev: bytes per row */
+/* d_out (2^(log_n + log_blowup) = N elements) = the polynomial sum_{i < n_coeffs} c_i X^i on the coset shift <w>, w =
+ * zk_fr_root_of_unity(N), in pair order: d_work[i] = c_i shift^i for i < n_coeffs and zero for n_coeffs <= i < N, zk_ntt_dev
+ * (forward, natural order in and out) in place on d_work, then d_out[2j] = d_work[j], d_out[2j+1] = d_work[j + N/2] for j < N/2.
+ * log_n >= 0, log_blowup >= 1, log_n + log_blowup <= ZK_FRI_MAX_LOG, n_coeffs <= 2^log_n; d_coeffs (n_coeffs elements) may be
+ * NULL when n_coeffs = 0, which gives N zeros.  d_work: N elements of scratch, holding the natural-order evaluations
+ * afterwards.  d_coeffs, d_work and d_out may not overlap one another.  The scale pass takes a second item per thread first at
+ * N = 2^19, the permutation (N/2 items, one 64-byte pair each) first at N = 2^20. */
+int zk_fri_lde_dev(int curve, int log_n, int log_blowup, uint64_t n_coeffs, const void* d_coeffs, const uint64_t* shift, void* d_work,
+                   void* d_out, void* stream);
+/* One fold of a layer of M = 2^log_m = 2h elements (d_in, pair order) into the next layer of h elements (d_out, pair order of
+ * h values: value j is stored at 2j for j < h/2 and at 2(j - h/2) + 1 otherwise; at h = 1 at 0), 1 <= log_m <= ZK_FRI_MAX_LOG:
+ *     value j = (d_in[2j] + d_in[2j+1]) / 2 + c w_inv^j (d_in[2j] - d_in[2j+1]),   j < h,
+ * which with c = alpha / (2 s) and w_inv = w^-1 is f'(x_j^2) for f' = f_even + alpha f_odd; the caller inverts 2 s and w once
+ * per layer (neither relation is checked).  Each thread reads one 64-byte pair; threads take a second item first at
+ * h = 2^19.  d_out may not overlap d_in. */
+int zk_fri_fold_dev(int curve, int log_m, const void* d_in, const uint64_t* c, const uint64_t* w_inv, void* d_out, void* stream);
+/* d_out (k rows) = rows d_indices[q], q < k, of the n_rows rows of row_bytes bytes at d_rows: the queried leaves of a layer in
+ * one launch.  An index >= n_rows takes row n_rows - 1 (as zk_merkle_paths_dev opens the last leaf).  1 <= n_rows <= 2^32;
+ * row_bytes is a multiple of 16, 16 <= row_bytes <= ZK_FRI_MAX_ROW_BYTES; k <= 2^32.  d_rows and d_out start at a multiple of
+ * 16, d_indices (k uint64, device memory) at a multiple of 8; d_out may not overlap d_rows or d_indices.  k = 0 is ZK_OK and
+ * launches nothing (d_indices and d_out may be NULL then; d_rows may not). */
+int zk_fri_rows_dev(uint64_t n_rows, uint64_t row_bytes, const void* d_rows, uint64_t k, const void* d_indices /* k uint64 */, void* d_out,
+                    void* stream);
+
 /* ---- GKR over layered circuits, the sparse side (csrc/gkr.hip) ----------------------------------------------------------
  * Layer j of a circuit has n_j wires and a dense table W_j of 2^k_j canonical Fr elements in device memory (zero beyond n_j),
  * 1 <= k_j <= ZK_GKR_MAX_LOG.  Gate g of layer j is (types[g]: 0 ADD / 1 MUL, in1[g], in2[g]) with in1, in2 < n_(j-1): three

@@ -51,11 +51,12 @@ def to_device(ops, polynomial):
 
 
 def _find(items, x):
-    """index of x: by identity first, by == only for Polynomial objects and points (`in` on a numpy array raises); -1 if absent"""
+    """index of x: by identity first, by == only for Polynomial objects, points and bytes (`in` on a numpy array raises); -1 if
+    absent"""
     for i, item in enumerate(items):
         if item is x:
             return i
-    if _is_polynomial(x) or ispointG1(x) or ispointG2(x):
+    if _is_polynomial(x) or ispointG1(x) or ispointG2(x) or isinstance(x, bytes):   # bytes: a hash commitment (FRI)
         for i, item in enumerate(items):
             if type(item) is type(x) and item == x:
                 return i

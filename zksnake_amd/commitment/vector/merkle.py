@@ -60,6 +60,23 @@ class MerkleTree:
         self._buf = buf   # the tree's one owner
         self.root = None if buf is None else buf.download((DIGEST,), np.uint8, (self.nodes - 1) * DIGEST).tobytes()
 
+    @classmethod
+    def from_device_rows(cls, n, ptr, row_bytes):
+        """the tree over n leaves that already lie in device memory, row_bytes bytes each from `ptr` on (hashed in place, not
+        modified, and not needed once this returns)"""
+        _leaf_count(n)
+        if not 0 <= row_bytes < 1 << 32:
+            raise ValueError("a leaf has fewer than 2^32 bytes")
+        lib = N.ensure_gpu()
+        tree = DeviceBuffer(_layout(n)[2] * DIGEST)
+        try:
+            N.check(lib.zk_blake2b_rows_dev(n, ptr, row_bytes, tree.ptr, None))
+            N.check(lib.zk_merkle_build_dev(n, tree.ptr, None))
+            return cls(n, tree)   # downloads the root
+        except BaseException:
+            tree.free()
+            raise
+
     def _device(self):
         if self._buf is None or self._buf.ptr is None:
             raise RuntimeError("the tree has been released")
