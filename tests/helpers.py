@@ -88,6 +88,42 @@ def build_device_harness(src, d, env_var=None, timeout=1500):
     return so
 
 
+# ---- stand-alone host programs: the host side of a HIP source under the address and undefined-behaviour sanitizers ----------
+def run_host_program(name, tmp_path, args=(), timeout=300):
+    """tests/native/<name>.cpp -> a program of its own, built and run: a host-only hipcc compile, an EMPTY offload bundle for the
+    __hip_fatbin_<hash> symbols the object refers to, link, run with every device hidden.  The sanitizer runtimes are linked into
+    the program; nothing is loaded into Python.  Returns the finished process (returncode, stdout, stderr); skips without hipcc."""
+    import os
+    import re
+    import shutil
+    import subprocess
+    import pytest
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    obj, stub, exe = str(tmp_path / f"{name}.o"), str(tmp_path / f"{name}_stub"), str(tmp_path / name)
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-mbmi2", "-madx",
+                           "-DZK_NOINLINE_MUL", *san, "-c", os.path.join(root, "tests", "native", name + ".cpp"), "-o", obj], timeout=600)
+    undefined = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout
+    syms = sorted(set(re.findall(r"__hip_fatbin_[0-9a-f]+", undefined)))
+    assert syms, "the host-only object names no device image"
+    magic = ",".join(f"'{c}'" for c in "__CLANG_OFFLOAD_BUNDLE__")
+    with open(stub + ".cpp", "w") as f:   # the magic string and a bundle count of zero: registered at load time, never looked into
+        f.write("#include <stdint.h>\nstruct bundle { char magic[24]; uint64_t count; };\n")
+        for sym in syms:
+            f.write(f'extern "C" __attribute__((aligned(4096))) const bundle {sym} = {{{{{magic}}}, 0}};\n')
+    subprocess.check_call(["g++", "-O0", "-c", stub + ".cpp", "-o", stub + ".o"], timeout=600)
+    subprocess.check_call([hipcc, "--offload-host-only", *san, "-o", exe, obj, stub + ".o"], timeout=600)
+    # on a machine with a GPU driver the HSA runtime starts up even with every device hidden and leaves 144 bytes of its own
+    # behind at exit; the leak check stays on for everything else
+    supp = tmp_path / "lsan.supp"
+    supp.write_text("leak:libhsa-runtime64\n")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", LSAN_OPTIONS=f"suppressions={supp}:print_suppressions=0")
+    return subprocess.run([exe, *map(str, args)], env=env, capture_output=True, text=True, timeout=timeout)
+
+
 # ---- multi-process tests: ranks as spawned children that report through a queue ---------------------------------------
 def rank_entry(worker, rank, q, args):
     """child side: run worker(rank, *args) -> result; the result or the child's traceback goes back through the queue"""

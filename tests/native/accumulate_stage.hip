@@ -1,7 +1,7 @@
 // Stage harness for stage 5 of the MSM pipeline: the PRODUCTION kernels of csrc/msm_accumulate.hip.h (accumulate_kernel,
-// accumulate_split_kernel, bases_to_mont_kernel) launched unchanged, with the grid expressions of stage_accumulate / MsmPlan::init
-// (msm_impl.hip.h), on layouts built by tests/test_gpu_msm_accumulate_stage.py.  Device build only (the library's own hipcc
-// pipeline, gfx950), driven through ctypes.  A second compilation of the header, with the default scheduling strategy for every
+// accumulate_split_kernel, bases_to_mont_kernel) through the launchers of that header (launch_accumulate, launch_bases_to_mont),
+// the same calls MsmPlan (msm_impl.hip.h) makes, on layouts built by tests/test_gpu_msm_accumulate_stage.py.  Device build only
+// (the library's own hipcc pipeline, gfx950), driven through ctypes.  A second compilation of the header, with the default scheduling strategy for every
 // group (the library compiles three of the groups' accumulate kernels with max-ilp scheduling): what is tested is the source.
 //   group: 0 BN254 G1, 1 BN254 G2, 2 BLS12-381 G1, 3 BLS12-381 G2
 // Returns 0, 1 for a refused argument, 3 for a HIP error, 4 for a layout under which the kernel would form an index outside one
@@ -62,18 +62,6 @@ static bool as_layout_inside(uint64_t n_rows, const uint32_t* sorted, uint64_t t
     return true;
 }
 
-template <class G>
-static void as_launch(bool split, uint64_t lanes_needed, const uint32_t* bases, const uint32_t* sorted, const uint32_t* bstart, const uint32_t* sstart,
-                      uint32_t n_keys, uint32_t seg_len, uint32_t prio, uint32_t* partials, uint32_t* buckets) {
-    if constexpr (AccumulateSplit<G>::ON) {
-        if (split) {
-            hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, 0, bases, sorted, bstart, sstart, n_keys, seg_len, prio, partials, buckets);
-            return;
-        }
-    }
-    hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, 0, bases, sorted, bstart, sstart, n_keys, seg_len, prio, partials, buckets);
-}
-
 // bases: n_rows affine rows (Montgomery, memory form); sorted: `total` entry words; bstart / sstart: n_keys + 1 words each;
 // partials: n_partials XYZZ rows, buckets: n_keys XYZZ rows -- both uploaded as given (the caller's sentinel) and read back.
 // split != 0: the lane-pair kernel (groups 1 and 3 only)
@@ -93,10 +81,10 @@ extern "C" int as_accumulate(int group, int split, const uint32_t* bases, uint64
     const uint64_t lanes_needed = (total + seg_len - 1) / seg_len;
     if (lanes_needed > 0) {   // stage_accumulate never runs on an empty entry list (a zero-size grid is not a launch)
         switch (group) {
-        case 0: as_launch<Bn254G1>(false, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p); break;
-        case 1: as_launch<Bn254G2>(split != 0, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p); break;
-        case 2: as_launch<Bls381G1>(false, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p); break;
-        default: as_launch<Bls381G2>(split != 0, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p); break;
+        case 0: launch_accumulate<Bn254G1>(false, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p, nullptr); break;
+        case 1: launch_accumulate<Bn254G2>(split != 0, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p, nullptr); break;
+        case 2: launch_accumulate<Bls381G1>(false, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p, nullptr); break;
+        default: launch_accumulate<Bls381G2>(split != 0, lanes_needed, d_bases.p, d_sorted.p, d_bstart.p, d_sstart.p, n_keys, seg_len, prio_steps, d_part.p, d_buckets.p, nullptr); break;
         }
     }
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 3;
@@ -105,19 +93,18 @@ extern "C" int as_accumulate(int group, int split, const uint32_t* bases, uint64
 }
 
 // in: n canonical affine rows; out: n rows in Montgomery form, or 2n rows (P_i, phi(P_i)) when glv != 0, read back over the
-// caller's sentinel.  Grid of MsmPlan::init.
+// caller's sentinel.
 extern "C" int as_bases_to_mont(int group, const uint32_t* in, uint64_t n, int glv, uint32_t* out) {
     if (!as_group_ok(group) || !in || !out || n == 0 || n > AS_MAX_COUNT || (glv != 0 && glv != 1)) return 1;
     const size_t AW = 2 * (size_t)as_words(group), n_out = (glv ? 2 : 1) * n;
     DevBuf d_in, d_out;
     int rc;
     if ((rc = as_upload(d_in, in, n * AW)) || (rc = as_upload(d_out, out, n_out * AW))) return rc;
-    const dim3 grid((unsigned)((n + 127) / 128)), block(128);
     switch (group) {
-    case 0: hipLaunchKernelGGL(bases_to_mont_kernel<Bn254G1>, grid, block, 0, 0, d_in.p, n, d_out.p, glv); break;
-    case 1: hipLaunchKernelGGL(bases_to_mont_kernel<Bn254G2>, grid, block, 0, 0, d_in.p, n, d_out.p, glv); break;
-    case 2: hipLaunchKernelGGL(bases_to_mont_kernel<Bls381G1>, grid, block, 0, 0, d_in.p, n, d_out.p, glv); break;
-    default: hipLaunchKernelGGL(bases_to_mont_kernel<Bls381G2>, grid, block, 0, 0, d_in.p, n, d_out.p, glv); break;
+    case 0: launch_bases_to_mont<Bn254G1>(d_in.p, n, d_out.p, glv, nullptr); break;
+    case 1: launch_bases_to_mont<Bn254G2>(d_in.p, n, d_out.p, glv, nullptr); break;
+    case 2: launch_bases_to_mont<Bls381G1>(d_in.p, n, d_out.p, glv, nullptr); break;
+    default: launch_bases_to_mont<Bls381G2>(d_in.p, n, d_out.p, glv, nullptr); break;
     }
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 3;
     return as_download(d_out, out, n_out * AW);

@@ -1,8 +1,8 @@
 // Stage harness for the lane-pair arithmetic behind the MSM's accumulate kernel: pair_add (csrc/pair.hip.h), the pair-split G2
 // bucket step sp_add_affine (csrc/fp2_split.hip.h) and the three PRODUCTION kernels of csrc/msm_reduce.hip.h (combine_kernel,
-// strided_sum_kernel, weighted_sum_kernel), launched unchanged with the grid / block / dynamic-LDS expressions of
-// msm_impl.hip.h (stage_accumulate, stage_reduce).  Device build only (the library's own hipcc pipeline, gfx950), driven through
-// ctypes by tests/test_gpu_msm_reduce_stages.py.
+// strided_sum_kernel, weighted_sum_kernel), launched through the launchers of that header (launch_combine, launch_strided_sum,
+// launch_weighted_sum), the same calls MsmPlan (msm_impl.hip.h) makes.  Device build only (the library's own hipcc pipeline,
+// gfx950), driven through ctypes by tests/test_gpu_msm_reduce_stages.py.
 //   group: 0 BN254 G1, 1 BN254 G2, 2 BLS12-381 G1, 3 BLS12-381 G2
 // Register form = the 29-bit limbs of Fp<P>::v as they sit in registers (F::REGS words per coordinate, Fp2 as c0 | c1); memory
 // form = packed 32-bit words (F::LIMBS per coordinate), a point as the XYZZ row [X | Y | ZZ | ZZZ].
@@ -198,20 +198,13 @@ extern "C" int rs_strided_sum(int group, const uint32_t* in, uint64_t n_in_point
     DevBuf d_in, d_out;
     int rc;
     if ((rc = rs_upload(d_in, in, n_in_points * XW)) || (rc = rs_upload(d_out, out, n_out_points * XW))) return rc;
-    const dim3 grid((unsigned)((((uint64_t)j0.n_out + j1.n_out) * lpo + 255) / 256)), block(256);
     switch (group) {
-    case 0: hipLaunchKernelGGL(strided_sum_kernel<Bn254G1>, grid, block, 0, 0, d_in.p, d_out.p, j0, j1, lpo); break;
-    case 1: hipLaunchKernelGGL(strided_sum_kernel<Bn254G2>, grid, block, 0, 0, d_in.p, d_out.p, j0, j1, lpo); break;
-    case 2: hipLaunchKernelGGL(strided_sum_kernel<Bls381G1>, grid, block, 0, 0, d_in.p, d_out.p, j0, j1, lpo); break;
-    default: hipLaunchKernelGGL(strided_sum_kernel<Bls381G2>, grid, block, 0, 0, d_in.p, d_out.p, j0, j1, lpo); break;
+    case 0: launch_strided_sum<Bn254G1>(d_in.p, d_out.p, j0, j1, lpo, nullptr); break;
+    case 1: launch_strided_sum<Bn254G2>(d_in.p, d_out.p, j0, j1, lpo, nullptr); break;
+    case 2: launch_strided_sum<Bls381G1>(d_in.p, d_out.p, j0, j1, lpo, nullptr); break;
+    default: launch_strided_sum<Bls381G2>(d_in.p, d_out.p, j0, j1, lpo, nullptr); break;
     }
     return rs_finish(d_out, out, n_out_points * XW);
-}
-
-template <class G>
-static void rs_launch_weighted(unsigned blocks, const uint32_t* in0, uint32_t m0, uint32_t n0, const uint32_t* in1, uint32_t m1, uint32_t* out) {
-    hipLaunchKernelGGL(weighted_sum_kernel<G>, dim3(blocks), dim3(HS_THREADS), (size_t)HalfRegs<typename G::F>::COUNT * HS_THREADS * 4, 0,
-                       in0, m0, n0, in1, m1, out);
 }
 
 // n0 arrays of m0 points in in0 and n0 arrays of m1 points in in1 (the row sums and the column sums of n0 bucket sets);
@@ -226,10 +219,10 @@ extern "C" int rs_weighted_sum(int group, const uint32_t* in0, uint32_t m0, uint
     if ((rc = rs_upload(d0, in0, (size_t)n0 * m0 * XW)) || (rc = rs_upload(d1, in1, (size_t)n0 * m1 * XW)) ||
         (rc = rs_upload(d_out, out, (size_t)blocks * 2 * XW))) return rc;
     switch (group) {
-    case 0: rs_launch_weighted<Bn254G1>(blocks, d0.p, m0, n0, d1.p, m1, d_out.p); break;
-    case 1: rs_launch_weighted<Bn254G2>(blocks, d0.p, m0, n0, d1.p, m1, d_out.p); break;
-    case 2: rs_launch_weighted<Bls381G1>(blocks, d0.p, m0, n0, d1.p, m1, d_out.p); break;
-    default: rs_launch_weighted<Bls381G2>(blocks, d0.p, m0, n0, d1.p, m1, d_out.p); break;
+    case 0: launch_weighted_sum<Bn254G1>(d0.p, m0, n0, d1.p, m1, d_out.p, nullptr); break;
+    case 1: launch_weighted_sum<Bn254G2>(d0.p, m0, n0, d1.p, m1, d_out.p, nullptr); break;
+    case 2: launch_weighted_sum<Bls381G1>(d0.p, m0, n0, d1.p, m1, d_out.p, nullptr); break;
+    default: launch_weighted_sum<Bls381G2>(d0.p, m0, n0, d1.p, m1, d_out.p, nullptr); break;
     }
     return rs_finish(d_out, out, (size_t)blocks * 2 * XW);
 }
@@ -251,13 +244,11 @@ extern "C" int rs_combine(int group, const uint32_t* partials, uint64_t n_partia
     int rc;
     if ((rc = rs_upload(d_part, partials, n_partials * XW)) || (rc = rs_upload(d_runs, run_start, (size_t)n_keys + 1)) ||
         (rc = rs_upload(d_list, big_list, n_keys)) || (rc = rs_upload(d_count, big_count, 2)) || (rc = rs_upload(d_buckets, buckets, n_keys * XW))) return rc;
-    const uint32_t small_blocks = (2 * n_keys + COMBINE_THREADS - 1) / COMBINE_THREADS;
-    const dim3 grid(small_blocks + COMBINE_WAVE_BLOCKS + COMBINE_BIG_BLOCKS), block(COMBINE_THREADS);
     switch (group) {
-    case 0: hipLaunchKernelGGL(combine_kernel<Bn254G1>, grid, block, 0, 0, d_part.p, d_runs.p, n_keys, small_blocks, d_list.p, d_count.p, d_buckets.p); break;
-    case 1: hipLaunchKernelGGL(combine_kernel<Bn254G2>, grid, block, 0, 0, d_part.p, d_runs.p, n_keys, small_blocks, d_list.p, d_count.p, d_buckets.p); break;
-    case 2: hipLaunchKernelGGL(combine_kernel<Bls381G1>, grid, block, 0, 0, d_part.p, d_runs.p, n_keys, small_blocks, d_list.p, d_count.p, d_buckets.p); break;
-    default: hipLaunchKernelGGL(combine_kernel<Bls381G2>, grid, block, 0, 0, d_part.p, d_runs.p, n_keys, small_blocks, d_list.p, d_count.p, d_buckets.p); break;
+    case 0: launch_combine<Bn254G1>(d_part.p, d_runs.p, n_keys, d_list.p, d_count.p, d_buckets.p, nullptr); break;
+    case 1: launch_combine<Bn254G2>(d_part.p, d_runs.p, n_keys, d_list.p, d_count.p, d_buckets.p, nullptr); break;
+    case 2: launch_combine<Bls381G1>(d_part.p, d_runs.p, n_keys, d_list.p, d_count.p, d_buckets.p, nullptr); break;
+    default: launch_combine<Bls381G2>(d_part.p, d_runs.p, n_keys, d_list.p, d_count.p, d_buckets.p, nullptr); break;
     }
     return rs_finish(d_buckets, buckets, n_keys * XW);
 }

@@ -1,6 +1,7 @@
 """Integer models and expected-value builders for the MSM reduction stages (tests/test_gpu_msm_reduce_stages.py): pair_add and
 the XYZZ doubling on Montgomery representatives (add-2008-s / dbl-2008-s-1, extending StepRef of test_field_edges.py), the SumJob
-index expression of strided_sum_kernel with the job shapes of stage_reduce, the run profiles of combine_kernel with the tier rule
+index expression of strided_sum_kernel with the job shapes of reduce_plan (csrc/msm_reduce_plan.h; tests/test_host_lib.py holds
+one_step_jobs / two_step_jobs against the C++ word for word), the run profiles of combine_kernel with the tier rule
 of the run-offset scan, and pools of input points whose discrete logarithms are known (expected sums are then (sum of logs) G,
 checked against chains of pyref.Group.add by the CPU tests).  Nothing here needs a GPU."""
 
@@ -377,14 +378,15 @@ class SumJob:
 
 
 def one_step_jobs(groups, R, C):
-    """rows and columns of `groups` bucket sets of R x C buckets (stage_reduce, msm_impl.hip.h)"""
+    """rows and columns of `groups` bucket sets of R x C buckets (the one-step form of reduce_plan, csrc/msm_reduce_plan.h)"""
     Bk = R * C
     n_rows, n_cols = groups * R, groups * C
     return SumJob(n_rows, R, Bk, C, 1, C, 0), SumJob(n_cols, C, Bk, 1, C, R, n_rows)
 
 
 def two_step_jobs(groups, R, C, K):
-    """(prow, pcol), (frow, fcol), lpo2: partial sums over runs of K buckets, then the sums of the partial sums"""
+    """(prow, pcol), (frow, fcol), lpo2: partial sums over runs of K buckets, then the sums of the partial sums (the two-step form
+    of reduce_plan)"""
     assert K >= 2 and C % K == 0 and R % K == 0 and C // K >= 2 and R // K >= 2
     Bk = R * C
     n_rows, n_cols = groups * R, groups * C

@@ -7,13 +7,12 @@ import json
 import os
 import random
 import re
-import shutil
-import subprocess
 
 import pytest
 
 import fri_model as M
 from test_fri_model import multi_case, rand_point, rand_poly, tamperings
+from helpers import run_host_program
 from zksnake_amd import _native as N
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,33 +39,12 @@ def as_proof(model_proof):
 
 
 def test_fri_host_side_refuses_bad_arguments_under_sanitizers(tmp_path):
-    """tests/native/fri_args_check.cpp, built by the recipe in its header exactly as tests/test_merkle_host.py builds
-    merkle_args_check: a host-only compile, an EMPTY offload bundle for the __hip_fatbin_<hash> symbol the object refers to, link,
+    """tests/native/fri_args_check.cpp, built by the recipe in its header (helpers.run_host_program, as tests/test_merkle_host.py
+    builds merkle_args_check): a host-only compile, an EMPTY offload bundle for the __hip_fatbin_<hash> symbol the object refers to, link,
     run.  The sanitizer runtimes are linked into the program; nothing is loaded into Python.  The program sees no device on any
     machine, so the calls that pass the checks fail in the launch with ZK_ERR_HIP, which is what it expects."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    magic = ",".join(f"'{c}'" for c in "__CLANG_OFFLOAD_BUNDLE__")
-    supp = tmp_path / "lsan.supp"      # the HSA runtime's own 144 bytes at exit on a machine with a GPU driver
-    supp.write_text("leak:libhsa-runtime64\n")
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", LSAN_OPTIONS=f"suppressions={supp}:print_suppressions=0")
-    name = "fri_args_check"
-    obj, stub, exe = str(tmp_path / f"{name}.o"), str(tmp_path / f"{name}_stub"), str(tmp_path / name)
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-mbmi2", "-madx",
-                           "-DZK_NOINLINE_MUL", *san, "-c", os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", obj], timeout=600)
-    undefined = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout
-    syms = sorted(set(re.findall(r"__hip_fatbin_[0-9a-f]+", undefined)))
-    assert syms, "the host-only object names no device image"
-    with open(stub + ".cpp", "w") as f:   # the magic string and a bundle count of zero: registered at load time, never looked into
-        f.write("#include <stdint.h>\nstruct bundle { char magic[24]; uint64_t count; };\n")
-        for sym in syms:
-            f.write(f'extern "C" __attribute__((aligned(4096))) const bundle {sym} = {{{{{magic}}}, 0}};\n')
-    subprocess.check_call(["g++", "-O0", "-c", stub + ".cpp", "-o", stub + ".o"], timeout=600)
-    subprocess.check_call([hipcc, "--offload-host-only", *san, "-o", exe, obj, stub + ".o"], timeout=600)
-    res = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0 and f"{name}: all ok" in res.stdout, res.stdout + res.stderr
+    res = run_host_program("fri_args_check", tmp_path)
+    assert res.returncode == 0 and "fri_args_check: all ok" in res.stdout, res.stdout + res.stderr
 
 
 def test_symbols_are_bound(lib):

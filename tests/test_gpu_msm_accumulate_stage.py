@@ -1,6 +1,6 @@
 """The accumulate kernels on hand-built layouts: tests/native/accumulate_stage.hip launches the PRODUCTION accumulate_kernel,
-accumulate_split_kernel and bases_to_mont_kernel (csrc/msm_accumulate.hip.h) with the grid expressions of msm_impl.hip.h on entry
-lists, bucket offsets and run offsets built here from (bucket sizes, seg_len), so that the alignments a scalar vector only meets by
+accumulate_split_kernel and bases_to_mont_kernel (csrc/msm_accumulate.hip.h) through that header's launch_accumulate and
+launch_bases_to_mont, the calls MsmPlan makes, on entry lists, bucket offsets and run offsets built here from (bucket sizes, seg_len), so that the alignments a scalar vector only meets by
 luck are all there: buckets that end exactly on a segment boundary, buckets of seg_len, seg_len +- 1, 2 seg_len, 2 seg_len + 1
 entries at offsets 0, 1 and seg_len - 1 inside a segment, more than 1500 empty keys before / between / after the non-empty ones,
 one key, totals of 1, seg_len - 1, seg_len and k seg_len + 1 entries, one entry per bucket.  Every run's slot (the run_slot rule as

@@ -1,6 +1,7 @@
 """The MSM bucket reduction stage by stage: tests/native/reduce_stages.hip runs pair_add (csrc/pair.hip.h) and sp_add_affine
 (csrc/fp2_split.hip.h) on raw register-form records, one lane PAIR per record, and launches the production kernels of
-csrc/msm_reduce.hip.h (combine_kernel, strided_sum_kernel, weighted_sum_kernel) unchanged on arrays built here.  References are
+csrc/msm_reduce.hip.h (combine_kernel, strided_sum_kernel, weighted_sum_kernel) on arrays built here, through the launchers of that
+header (launch_combine, launch_strided_sum, launch_weighted_sum) that MsmPlan calls, so with the plan's own grids.  References are
 plain integers (tests/reduce_model.py): add-2008-s / dbl-2008-s-1 on Montgomery representatives for the additions, sums of known
 multiples of the generator (held against chains of pyref additions on the CPU) for the kernels.  No tolerance: exact integers.
 
@@ -73,7 +74,7 @@ def test_model_pair_add_against_pyref(G):
 
 
 def test_sum_job_index_against_enumeration():
-    """SumJob.index with the job shapes of stage_reduce against the definition: row r of bucket set g sums buckets g B + r C + [0, C),
+    """SumJob.index with the job shapes of reduce_plan (csrc/msm_reduce_plan.h) against the definition: row r of bucket set g sums buckets g B + r C + [0, C),
     column c sums g B + [0, R) C + c; the two-step form reaches the same buckets through its partial sums"""
     for groups, R, C in ((1, 4, 8), (3, 8, 4), (2, 5, 3), (2, 8, 16)):
         Bk = R * C

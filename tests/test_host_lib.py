@@ -262,39 +262,137 @@ def test_ntt_pass_plan_equals_its_integer_model(tmp_path):
         assert line == f"{log_n}:" + "".join(f" {m},{q}" for m, q in qap_model.plan(log_n)), line
 
 
+def test_msm_reduce_plan_equals_its_integer_model(tmp_path):
+    """reduce_shape / reduce_plan (csrc/msm_reduce_plan.h), which MsmPlan sizes its buffers and launches its strided sums from,
+    printed by tests/native/reduce_plan_check.cpp and compared word for word with reduce_model.one_step_jobs / two_step_jobs, the
+    copies the GPU stage tests build their arrays from, plus the selection rule and the shape written out here: c = 2 .. 20 (17
+    and 20 wide), 1 .. 16 bucket sets (which crosses 2^18 buckets both ways at c = 16), both settings of sum_one_step, three of
+    lanes_per_output.  A host program under the address and undefined-behaviour sanitizers, their runtimes linked in; no GPU."""
+    import subprocess
+    import reduce_model as M
+    exe = str(tmp_path / "reduce_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                           "-static-libubsan", "-o", exe, os.path.join(ROOT, "tests", "native", "reduce_plan_check.cpp")])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert res.returncode == 0, res.stdout + res.stderr
+    lines = res.stdout.splitlines()
+    cases = [(c, groups, one_step, lpo) for c in (2, 3, 4, 9, 15, 16, 17, 20) for groups in (1, 2, 8, 16) for one_step in (0, 1) for lpo in (0, 2, 64)]
+    assert len(lines) == len(cases)
+    step_counts = set()
+    for (c, groups, one_step, lpo_opt), line in zip(cases, lines):
+        wide = c > 16
+        B = 1 << (c - 1)
+        R = 1 << min(-(-(c - 1) // 2), 20 if wide else 8)   # 2^ceil((c - 1) / 2), at most 2^8 unless wide
+        C = B // R
+        K = 16 if R >= 64 and C >= 64 else 0
+        two = not one_step and groups * B >= 1 << 18 and K >= 2 and C % K == 0 and R % K == 0 and C // K >= 2 and R // K >= 2
+        if two:
+            (prow, pcol), (frow, fcol), lpo2 = M.two_step_jobs(groups, R, C, K)
+            steps = [(prow, pcol, 2), (frow, fcol, lpo2)]
+        else:
+            rows, cols = M.one_step_jobs(groups, R, C)
+            steps = [(rows, cols, lpo_opt or (32 if groups * (R + C) >= 4096 else 64))]
+        want = f"{c} {int(wide)} {groups} {one_step} {lpo_opt}: {B} {R} {C} {-(-R // 128)} {-(-C // 128)} {K} | {len(steps)}"
+        for j0, j1, lpo in steps:
+            want += " | " + " ".join(str(int(w)) for w in list(j0.words()) + list(j1.words()) + [lpo])
+        assert line == want, (line, want)
+        step_counts.add((c, groups, len(steps)))
+    # the threshold is crossed both ways at c = 16, and a wide set takes two steps on its own
+    assert {(16, 2, 1), (16, 8, 2), (20, 1, 2), (15, 16, 2), (15, 8, 1)} <= step_counts
+
+
+def _tail_shape(c, wide):
+    """R, C, weighted-sum blocks per row array and per column array, log2 C: the reduction shape of c-bit windows"""
+    R = 1 << min(-(-(c - 1) // 2), 20 if wide else 8)
+    C = (1 << (c - 1)) // R
+    return R, C, -(-R // 128), -(-C // 128), C.bit_length() - 1
+
+
+def _tail_scalar(s, c, shape_c, wide, groups, q_first, pre):
+    """the multiple of the generator msm_host_tail must return when block i of h_final is s[i] G, from the formula in its comment:
+    per bucket set W = 2^(lc+7) X_R + 2^lc sum S_k + 2^7 X_C + (sum S'_k + sum T_k), X = sum_k k T_k, over the row blocks (S_k, T_k)
+    and the column blocks (S'_k, T'_k); total = sum_g 2^(c (q_first + g)) W_g, or W_0 alone in fixed-base mode"""
+    _, _, bpr, bpc, lc = _tail_shape(shape_c, wide)
+    assert len(s) == 2 * groups * (bpr + bpc)
+    total = 0
+    for g in range(groups):
+        rows = [(s[(g * bpr + k) * 2], s[(g * bpr + k) * 2 + 1]) for k in range(bpr)]
+        cols = [(s[(groups * bpr + g * bpc + k) * 2], s[(groups * bpr + g * bpc + k) * 2 + 1]) for k in range(bpc)]
+        x_r, x_c = sum(k * t for k, (_, t) in enumerate(rows)), sum(k * t for k, (_, t) in enumerate(cols))
+        w = (x_r << (lc + 7)) + (sum(sk for sk, _ in rows) << lc) + (x_c << 7) + sum(sk for sk, _ in cols) + sum(t for _, t in rows)
+        total += w if pre else w << (c * (q_first + g))
+    return total
+
+
+def test_msm_host_tail_against_integers(tmp_path):
+    """msm_host_tail (csrc/msm_host_tail.h), the stage between the last kernel of an MSM and its result, for all four groups on
+    blocks that are known multiples s_i G (tests/native/host_tail_check.cpp builds them with the library's own host arithmetic):
+    the affine point it returns must be (the integer formula of _tail_scalar) G by pyref, exactly.  Shapes: c = 4 (one block per
+    array), c = 16 (two row blocks), c = 20 fixed-base (eight row blocks, four column blocks); general mode with 1 and 3 bucket sets
+    and q_first 0 and 2.  Inputs: random multiples with a quarter of the blocks at infinity; one block solved for so that the total
+    is infinity; every block the same point (the additions double); blocks alternating between a point and its negative (they
+    cancel); every block at infinity.  The refusal "reduction layout does not fit the window" is asked for once; no shape of
+    reduce_shape reaches it (lc + 7 <= c for every c with more than one row block), so the case pairs the blocks of c = 16 with
+    13-bit windows.  A host program under the address and undefined-behaviour sanitizers, their runtimes linked in; no GPU."""
+    import subprocess
+    import reduce_model as M
+    exe = str(tmp_path / "host_tail_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                           "-static-libubsan", "-o", exe, os.path.join(ROOT, "tests", "native", "host_tail_check.cpp")], timeout=600)
+    rnd = random.Random(8)
+    configs = [(c, 0, groups, q_first, 0) for c in (4, 16) for groups in (1, 3) for q_first in (0, 2)] + [(20, 1, 1, 0, 1)]
+    cases = []
+    for G in M.GROUPS:
+        for c, wide, groups, q_first, pre in configs:
+            kinds = ["mixed", "total_inf"] + (["equal", "opposite", "all_inf"] if groups == 1 and q_first == 0 else [])
+            for kind in kinds:
+                _, _, bpr, bpc, _ = _tail_shape(c, wide)
+                n = 2 * groups * (bpr + bpc)
+                a = rnd.randrange(1, 1 << 64)
+                if kind == "mixed":
+                    s = [0 if rnd.random() < 0.25 else rnd.randrange(1, 1 << 64) for _ in range(n)]
+                elif kind == "total_inf":
+                    # the first column block's S of set 0 enters the total with the factor 2^(c q_first) (1 in fixed-base mode)
+                    s = [rnd.randrange(1, 1 << 64) for _ in range(n)]
+                    fix = 2 * groups * bpr
+                    s[fix] = 0
+                    rest = _tail_scalar(s, c, c, wide, groups, q_first, pre)
+                    s[fix] = -rest * pow(1 if pre else 1 << (c * q_first), -1, G.r) % G.r
+                elif kind == "equal":
+                    s = [a] * n
+                elif kind == "opposite":
+                    s = [a if i % 2 == 0 else G.r - a for i in range(n)]
+                else:
+                    s = [0] * n
+                cases.append((G, kind, (c, c, wide, groups, q_first, pre), s))
+    G0 = M.GROUPS[0]
+    refusal = (G0, "refusal", (13, 16, 0, 2, 0, 0), [rnd.randrange(1, 1 << 64) for _ in range(2 * 2 * 3)])
+    text = "".join(f"{G.gid} {' '.join(map(str, cfg))} {len(s)}\n" + "".join(f"{v:x}\n" for v in s) for G, _, cfg, s in cases + [refusal])
+    res = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout + res.stderr
+    lines = res.stdout.splitlines()
+    assert len(lines) == len(cases) + 1
+    infinities = 0
+    for (G, kind, cfg, s), line in zip(cases, lines):
+        want = G.mul_gen(_tail_scalar(s, *cfg))
+        flat = [0] * (2 * G.d) if want is None else [v for coord in want for v in G.comp(coord)]
+        assert [int(x, 16) for x in line.split()] == flat, (G, kind, cfg, line)
+        infinities += want is None
+        assert (want is None) == (kind in ("total_inf", "all_inf")) or kind == "opposite", (G, kind, cfg)
+    assert infinities >= 4 * (len(configs) + 3)
+    assert lines[-1] == "refused: internal: reduction layout does not fit the window", lines[-1]
+
+
 def test_protocol_host_sides_refuse_bad_arguments_under_sanitizers(tmp_path):
     """the host side of csrc/ipa.hip and csrc/rangeproof.hip (argument rules, overlap checks, the conversion of the challenges,
     the shared pieces of fr_sum.hip.h and ipa_chain.hip.h) as two stand-alone programs under the address and undefined-behaviour
-    sanitizers (tests/native/ipa_args_check.cpp, rangeproof_args_check.cpp, built by the recipe in their headers): a host-only
-    compile, an EMPTY offload bundle for the __hip_fatbin_<hash> symbol the object refers to, link, run.  The sanitizer runtimes
-    are linked into the programs.  A program sees no device on any machine, so the calls that pass the checks fail in the
+    sanitizers (tests/native/ipa_args_check.cpp, rangeproof_args_check.cpp, built by the recipe in their headers, which
+    helpers.run_host_program carries out): a host-only compile, an EMPTY offload bundle for the __hip_fatbin_<hash> symbol the
+    object refers to, link, run.  The sanitizer runtimes are linked into the programs.  A program sees no device on any machine, so the calls that pass the checks fail in the
     launch with ZK_ERR_HIP, which is what it expects."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    magic = ",".join(f"'{c}'" for c in "__CLANG_OFFLOAD_BUNDLE__")
-    # on a machine with a GPU driver the HSA runtime starts up even with every device hidden and leaves 144 bytes of its own
-    # behind at exit; the leak check stays on for everything else
-    supp = tmp_path / "lsan.supp"
-    supp.write_text("leak:libhsa-runtime64\n")
-    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="", LSAN_OPTIONS=f"suppressions={supp}:print_suppressions=0")
+    from helpers import run_host_program
     for name in ("ipa_args_check", "rangeproof_args_check"):
-        obj, stub, exe = str(tmp_path / f"{name}.o"), str(tmp_path / f"{name}_stub"), str(tmp_path / name)
-        subprocess.check_call([hipcc, "-x", "hip", "--offload-host-only", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-mbmi2", "-madx",
-                               "-DZK_NOINLINE_MUL", *san, "-c", os.path.join(ROOT, "tests", "native", name + ".cpp"), "-o", obj], timeout=600)
-        undefined = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout
-        syms = sorted(set(re.findall(r"__hip_fatbin_[0-9a-f]+", undefined)))
-        assert syms, "the host-only object names no device image"
-        with open(stub + ".cpp", "w") as f:   # the magic string and a bundle count of zero: registered at load time, never looked into
-            f.write("#include <stdint.h>\nstruct bundle { char magic[24]; uint64_t count; };\n")
-            for sym in syms:
-                f.write(f'extern "C" __attribute__((aligned(4096))) const bundle {sym} = {{{{{magic}}}, 0}};\n')
-        subprocess.check_call(["g++", "-O0", "-c", stub + ".cpp", "-o", stub + ".o"], timeout=600)
-        subprocess.check_call([hipcc, "--offload-host-only", *san, "-o", exe, obj, stub + ".o"], timeout=600)
-        res = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
+        res = run_host_program(name, tmp_path)
         assert res.returncode == 0 and f"{name}: all ok" in res.stdout, res.stdout + res.stderr
 
 

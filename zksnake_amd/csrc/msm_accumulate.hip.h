@@ -208,4 +208,29 @@ __global__ void bases_to_mont_kernel(const uint32_t* __restrict__ in, uint64_t n
     store_affine<F>(out + i * AW, p);
 }
 
+// ---- host: one launcher per kernel ------------------------------------------------------------------------------------
+// The only copy of each kernel's grid / block expression: MsmPlan (msm_impl.hip.h) and the stage harness
+// (tests/native/accumulate_stage.hip) launch through these.  Errors are the caller's to collect (hipGetLastError).
+
+// one lane per segment of seg_len sorted entries, `lanes_needed` segments; split: a lane PAIR per segment (Fp2 groups only)
+template <class G>
+inline void launch_accumulate(bool split, uint64_t lanes_needed, const uint32_t* bases, const uint32_t* sorted, const uint32_t* bucket_start,
+                              const uint32_t* run_start, uint32_t n_keys, uint32_t seg_len, uint32_t prio_steps, uint32_t* partials,
+                              uint32_t* buckets, hipStream_t st) {
+    if constexpr (AccumulateSplit<G>::ON) {
+        if (split) {
+            hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, st, bases, sorted,
+                               bucket_start, run_start, n_keys, seg_len, prio_steps, partials, buckets);
+            return;
+        }
+    }
+    hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, st, bases, sorted, bucket_start,
+                       run_start, n_keys, seg_len, prio_steps, partials, buckets);
+}
+
+template <class G>
+inline void launch_bases_to_mont(const uint32_t* in, uint64_t n, uint32_t* out, int glv, hipStream_t st) {
+    hipLaunchKernelGGL(bases_to_mont_kernel<G>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, in, n, out, glv);
+}
+
 }  // namespace zkmi

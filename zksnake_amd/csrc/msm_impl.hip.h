@@ -8,7 +8,9 @@
 // is bit-identical with the reference's.
 //
 // Pipeline (one stream, no host round trip until the tail); stages 1-4 do not depend on the group and live in MsmFront
-// (msm_front.h, compiled once in msm_front.hip), stages 5-8 in MsmPlan<G> below:
+// (msm_front.h, compiled once in msm_front.hip), stages 5-8 are MsmPlan<G>'s below.  The plan holds the buffers, the options and the
+// state of a run; each stage's kernels and launchers (msm_accumulate.hip.h, msm_reduce.hip.h), the reduction geometry
+// (msm_reduce_plan.h) and the host tail (msm_host_tail.h) are written once in their own headers, where the stage tests call them too:
 //   1. digits      scalar -> signed c-bit window digits (bias trick: s + sum 2^(c-1) 2^(wc),
 //                  then plain bit fields), 2 B per (window, scalar), coalesced.
 //   2. histogram   one workgroup per (window, chunk): 2^(c-1) counters live in LDS (128 KiB at
@@ -39,6 +41,7 @@
 #include "msm_common.hip.h"
 #include "msm_accumulate.hip.h"
 #include "msm_reduce.hip.h"
+#include "msm_host_tail.h"
 
 namespace zkmi {
 using mem::DevBuf;
@@ -151,6 +154,8 @@ struct MsmPlan : MsmPlanBase {
     static constexpr uint64_t SEG_TARGET_LANES = 256ull * 1024;  // 4 waves per SIMD on 256 CUs
     static constexpr int MAX_C = 20;           // widest window (fixed-base plans; digits are then 32-bit)
     bool wide = false;                         // c > 16: 32-bit digits, two-level sort only
+    enum class Phase { All, SortOnly, Rest };     // what one call of run_stages puts on the stream
+    enum class Run { Idle, Sorted, Pending };     // Sorted: enqueue_sort done, enqueue_rest still to come; Pending: finish() to come
 
     // device workspace of one run (stages 5..7; the sort's is the front's)
     struct Work {
@@ -174,8 +179,7 @@ struct MsmPlan : MsmPlanBase {
     bool glv = false;    // general G1 plan over (P_i, phi(P_i)) with half-length scalars
     bool pre = false;  // ZK_MSM_PRECOMPUTE: shared bucket set over a table of 2^(c w) P_i
     int pw_first = 0, pw_count = 0;  // windows this plan can run (a sharded rank's share; all of them by default)
-    uint32_t B = 0, R = 0, C = 0;
-    uint32_t bpr = 0, bpc = 0;       // weighted-sum blocks per row array / per column array
+    ReduceShape shape;               // buckets per set as rows x columns, weighted-sum blocks (msm_reduce_plan.h)
     Work ws;
     MsmFront front;  // stages 1-4: scalars -> digits -> sorted entry list
     // shared device buffers
@@ -224,14 +228,7 @@ struct MsmPlan : MsmPlanBase {
         if (win_first < 0 || win_first + win_count > nwin) return fail(ZK_ERR_ARG, "window range out of bounds");
         pw_first = win_first;
         pw_count = win_count;
-        B = 1u << (c - 1);
-        int rl = (c - 1 + 1) / 2;
-        if (rl > 8 && !wide) rl = 8;
-        R = 1u << rl;
-        C = B / R;
-        if (C > 1024 || R > 1024) return fail(ZK_ERR_ARG, "window too wide for the reduction stage");
-        bpr = (R + WS_BLOCK - 1) / WS_BLOCK;
-        bpc = (C + WS_BLOCK - 1) / WS_BLOCK;
+        if (!reduce_shape(c, wide, &shape)) return fail(ZK_ERR_ARG, "window too wide for the reduction stage");
         const uint64_t entries = (uint64_t)pw_count * n;
         if (entries > 0x7FFFFFFFull) return fail(ZK_ERR_ARG, "MSM too large");
 
@@ -244,13 +241,12 @@ struct MsmPlan : MsmPlanBase {
             ZK_HIP_RC(bases_block->alloc((pre ? (uint64_t)pw_count : 1ull) * n * AW * 4));
             d_bases = bases_block->as();
             if (bases_on_device) {
-                hipLaunchKernelGGL(bases_to_mont_kernel<G>, dim3((unsigned)((n_api + 127) / 128)), dim3(128), 0, 0,
-                                   (const uint32_t*)bases, n_api, d_bases, glv ? 1 : 0);
+                launch_bases_to_mont<G>((const uint32_t*)bases, n_api, d_bases, glv ? 1 : 0, nullptr);
             } else {
                 DevBuf tmp;
                 ZK_HIP_RC(tmp.alloc(n_api * AW * 4));
                 ZK_HIP(hipMemcpy(tmp.as(), bases, n_api * AW * 4, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(bases_to_mont_kernel<G>, dim3((unsigned)((n_api + 127) / 128)), dim3(128), 0, 0, tmp.as(), n_api, d_bases, glv ? 1 : 0);
+                launch_bases_to_mont<G>(tmp.as(), n_api, d_bases, glv ? 1 : 0, nullptr);
                 ZK_HIP(hipDeviceSynchronize());
             }
             ZK_HIP(hipGetLastError());
@@ -263,43 +259,36 @@ struct MsmPlan : MsmPlanBase {
         mark("stream + bases");
         {
             FrontLayout fl;
-            fl.c = c; fl.B = B; fl.n = n; fl.n_api = n_api; fl.pre = pre; fl.wide = wide; fl.glv = glv ? &GlvOf<G>::P::K : nullptr;
+            fl.c = c; fl.B = shape.B; fl.n = n; fl.n_api = n_api; fl.pre = pre; fl.wide = wide; fl.glv = glv ? &GlvOf<G>::P::K : nullptr;
             fl.pw_first = pw_first; fl.pw_count = pw_count; fl.nwin = nwin; fl.curve = G::CURVE;
             ZK_HIP_RC(front.init(fl, &opt));
         }
         const uint64_t max_sets = pre ? 1ull : (uint64_t)pw_count;
-        ZK_HIP_RC(pinned_alloc_cached((void**)&h_final, (size_t)max_sets * (bpr + bpc) * 2 * XW * 4));
+        ZK_HIP_RC(pinned_alloc_cached((void**)&h_final, (size_t)max_sets * shape.blocks() * 2 * XW * 4));
         mark("scalars/digits/pinned");
         ZK_HIP(hipEventCreateWithFlags(&ev_start, hipEventDisableSystemFence));   // timing only: nothing synchronises with it
         ZK_HIP(hipEventCreate(&ev_end));
         {
-            const uint64_t keys = max_sets * B;
+            const uint64_t keys = max_sets * shape.B;
             // a window-range run picks its own (shorter) segments: at most SEG_TARGET_LANES of them, or entries / 8
             const uint32_t seg_full = pick_seg_len(entries);
             const uint64_t max_segs = std::max<uint64_t>(entries / seg_full, std::min<uint64_t>(entries / 8, seg_lanes_at_init)) + keys + 8;
             ZK_HIP_RC(front.alloc_workspace());
             ZK_HIP_RC(ws.partials.alloc(max_segs * XW * 4));
             ZK_HIP_RC(ws.buckets.alloc(keys * XW * 4));
-            ZK_HIP_RC(ws.rows.alloc(max_sets * (R + C) * XW * 4));
-            if (sum_part_len() >= 2) ZK_HIP_RC(ws.parts.alloc(max_sets * 2 * (uint64_t)(B / sum_part_len()) * XW * 4));
-            ZK_HIP_RC(ws.fin.alloc(max_sets * (bpr + bpc) * 2 * XW * 4));
+            ZK_HIP_RC(ws.rows.alloc(max_sets * (shape.R + shape.C) * XW * 4));
+            if (reduce_parts_per_set(shape)) ZK_HIP_RC(ws.parts.alloc(max_sets * reduce_parts_per_set(shape) * XW * 4));
+            ZK_HIP_RC(ws.fin.alloc(max_sets * shape.blocks() * 2 * XW * 4));
             for (hipEvent_t* e : {&ws.ev_acc0, &ws.ev_accs, &ws.ev_acc1, &ws.ev_release}) ZK_HIP(hipEventCreate(e));
         }
         mark("workspace + events");
         // LDS above 64 KiB needs the opt-in
         ZK_HIP_RC(front.set_kernel_attributes());
-        ZK_HIP(hipFuncSetAttribute((const void*)weighted_sum_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(HalfRegs<F>::COUNT * HS_THREADS * 4)));
+        ZK_HIP(weighted_sum_set_attributes<G>());
         mark("func attributes");
         ZK_HIP(hipDeviceSynchronize());
         mark("device sync");
         return ZK_OK;
-    }
-
-    // buckets one lane pair adds up in the first step of the two-step strided sums (0 = one step)
-    uint32_t sum_part_len() const {
-        const uint32_t k = 16u;
-        return (R >= 4 * k && C >= 4 * k) ? k : 0u;
     }
 
     // Segment length for a run over `entries` sorted entries: aim at >= 4 waves per SIMD worth of lanes (a window-range
@@ -312,7 +301,7 @@ struct MsmPlan : MsmPlanBase {
         if (sl > 64) sl = 64;
         if (pre) {
             // shared bucket set: keep a bucket within ~12 runs so that one lane pair can combine it
-            uint64_t per_bucket = entries / B;
+            uint64_t per_bucket = entries / shape.B;
             uint64_t want = (per_bucket + 11) / 12;
             if (want > sl) sl = want;
             if (sl > 1024) sl = 1024;
@@ -322,26 +311,21 @@ struct MsmPlan : MsmPlanBase {
 
     // ---- the stages of one run after the front's, for the windows [ws.w_first, ws.w_first + ws.w_count) on stream st -----------
 
+    // the pair-split accumulate kernel (Fp2 groups) or the one-lane one: the plan's option, else the group's default
+    bool split_pairs_on() const {
+        if constexpr (AccumulateSplit<G>::ON) return opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0;
+        return false;
+    }
+
     // stage 5: the dominant kernel; stage 6: buckets whose entries span several segments (three tiers, one launch)
     int stage_accumulate(uint32_t m, const SortedView& sv, hipStream_t st, bool prio_steps) {
         Work& l = ws;
-        uint32_t *const partials = l.partials.as(), *const buckets = l.buckets.as();
-        const uint32_t seg_len = sv.seg_len;
-        const uint32_t n_keys = l.groups * B;
-        const uint64_t lanes_needed = ((uint64_t)l.w_count * m + seg_len - 1) / seg_len;
-        bool launched = false;
-        if constexpr (AccumulateSplit<G>::ON) {
-            if (opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0) {
-                // Fp2 groups: a lane PAIR per segment, every value split by component (fp2_split.hip.h)
-                hipLaunchKernelGGL(accumulate_split_kernel<G>, dim3((unsigned)((2 * lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, partials, buckets);
-                launched = true;
-            }
-        }
-        if (!launched) hipLaunchKernelGGL(accumulate_kernel<G>, dim3((unsigned)((lanes_needed + 255) / 256)), dim3(256), 0, st, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, seg_len, prio_steps ? 1u : 0u, partials, buckets);
+        const uint32_t n_keys = l.groups * shape.B;
+        const uint64_t lanes_needed = ((uint64_t)l.w_count * m + sv.seg_len - 1) / sv.seg_len;
+        launch_accumulate<G>(split_pairs_on(), lanes_needed, d_bases, sv.sorted, sv.bstart, sv.sstart, n_keys, sv.seg_len, prio_steps ? 1u : 0u,
+                             l.partials.as(), l.buckets.as(), st);
         ZK_HIP(hipEventRecord(l.ev_acc1, st));
-        const uint32_t small_blocks = (2 * n_keys + COMBINE_THREADS - 1) / COMBINE_THREADS;
-        hipLaunchKernelGGL(combine_kernel<G>, dim3(small_blocks + COMBINE_WAVE_BLOCKS + COMBINE_BIG_BLOCKS), dim3(COMBINE_THREADS), 0, st,
-                           partials, sv.sstart, n_keys, small_blocks, sv.big_list, sv.big_count, buckets);
+        launch_combine<G>(l.partials.as(), sv.sstart, n_keys, sv.big_list, sv.big_count, l.buckets.as(), st);
         ZK_HIP(hipGetLastError());
         return ZK_OK;
     }
@@ -349,70 +333,47 @@ struct MsmPlan : MsmPlanBase {
     // stage 7: sum_b (b + 1) B_b per bucket set down to (S, T) per block of row / column sums, copied to h_final
     int stage_reduce(hipStream_t st) {
         Work& l = ws;
-        uint32_t *const buckets = l.buckets.as(), *const parts = l.parts.as(), *const row_sums = l.rows.as(), *const fin = l.fin.as();
         const uint32_t groups = l.groups;
-        const uint32_t n_keys = groups * B;
-        // 7. reduce: rows (sum over lo), cols (sum over hi), weighted sums
-        uint32_t n_rows = groups * R, n_cols = groups * C;
-        SumJob rows = {n_rows, R, B, C, 1u, C, 0u};
-        SumJob cols = {n_cols, C, B, 1u, C, R, n_rows};
-        // Two steps when the sums are long: one lane pair walks a run of K buckets with no idle lanes (the tree of the
-        // one-step form leaves half of its lane-steps empty), then a short tree adds the R / K or C / K partial sums.
-        const bool one_step = opt.sum_one_step;  // A/B knob
-        // worth it from 2^18 buckets on (8 windows of 2^15, or the 2^19-bucket set of a fixed-base plan): with fewer the sums
-        // are a latency chain and the second launch only lengthens it (measured: 2^17 buckets 0.223 vs 0.212 ms)
-        const uint32_t K = (one_step || n_keys < (1u << 18)) ? 0u : sum_part_len();
-        if (K >= 2 && parts && C % K == 0 && R % K == 0 && C / K >= 2 && R / K >= 2) {
-            const uint32_t pr = C / K, pc = R / K;  // partial sums per row sum / per column sum
-            // step 1: partial (row r, part p) = sum of buckets r C + p K + [0, K); (column j, part p) = sum of (p K + i) C + j
-            SumJob prow = {n_rows * pr, R * pr, B, C, 1u, K, 0u, pr, K};
-            SumJob pcol = {n_cols * pc, C * pc, B, 1u, C, K, n_rows * pr, pc, K * C};
-            hipLaunchKernelGGL(strided_sum_kernel<G>, dim3((unsigned)((((uint64_t)prow.n_out + pcol.n_out) * 2 + 255) / 256)), dim3(256), 0, st, buckets, parts, prow, pcol, 2u);
-            // step 2: contiguous runs of pr (pc) partial sums
-            SumJob frow = {n_rows, n_rows, 0u, pr, 1u, pr, 0u};
-            SumJob fcol = {n_cols, n_cols, 0u, pc, 1u, pc, n_rows, 1u, 0u, n_rows * pr};
-            const uint32_t lpo2 = 2 * std::min<uint32_t>(32u, std::max(pr, pc) / 2);
-            hipLaunchKernelGGL(strided_sum_kernel<G>, dim3(((n_rows + n_cols) * lpo2 + 255) / 256), dim3(256), 0, st, parts, row_sums, frow, fcol, lpo2);
-        } else {
-        // lanes per output (two lanes = one point): many outputs (one bucket set per window) -> 16 pairs each walk
-        // count/16 buckets and finish with a 4-level tree; few outputs (shared bucket set) -> 32 pairs, shortest chain
-        const uint32_t lpo_env = opt.lanes_per_output;
-        const uint32_t lpo = lpo_env ? lpo_env : ((n_rows + n_cols) >= 4096 ? 32u : 64u);
-        hipLaunchKernelGGL(strided_sum_kernel<G>, dim3(((n_rows + n_cols) * lpo + 255) / 256), dim3(256), 0, st, buckets, row_sums, rows, cols, lpo);
+        const ReducePlan plan = reduce_plan(shape, groups, opt.sum_one_step, opt.lanes_per_output);
+        uint32_t* const row_sums = l.rows.as();
+        const uint32_t* in = l.buckets.as();
+        for (int k = 0; k < plan.steps; ++k) {
+            uint32_t* const out = k + 1 < plan.steps ? l.parts.as() : row_sums;
+            launch_strided_sum<G>(in, out, plan.step[k].rows, plan.step[k].cols, plan.step[k].lpo, st);
+            in = out;
         }
-        hipLaunchKernelGGL(weighted_sum_kernel<G>, dim3(groups * (bpr + bpc)), dim3(HS_THREADS), (size_t)HalfRegs<F>::COUNT * HS_THREADS * 4, st,
-                           row_sums, R, groups, row_sums + (size_t)n_rows * XW, C, fin);
+        launch_weighted_sum<G>(row_sums, shape.R, groups, row_sums + (size_t)groups * shape.R * XW, shape.C, l.fin.as(), st);
         ZK_HIP(hipGetLastError());
-        ZK_HIP(hipMemcpyAsync(h_final, fin, (size_t)groups * (bpr + bpc) * 2 * XW * 4, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(h_final, l.fin.as(), (size_t)groups * shape.blocks() * 2 * XW * 4, hipMemcpyDeviceToHost, st));
         return ZK_OK;
     }
 
     // stages 2..7 + D2H
     // `borrowed`: the digits and the sort of another plan's run over the same scalars (enqueue_shared); stages 1-4 are skipped
-    // phase: 0 = everything, 1 = up to the sorted entry list only, 2 = from the accumulate kernel on (after phase 1).
+    // phase: All, SortOnly = up to the sorted entry list only, Rest = from the accumulate kernel on (after SortOnly).
     // gate: waited for right before the accumulate kernel (another plan's accumulate has finished), so that the
     // accumulate kernels of several plans run one after the other while their sorts and reductions overlap.
-    int run_stages(uint32_t m, uint32_t dstride, hipStream_t st, const SortExport* borrowed = nullptr, int phase = 0, hipEvent_t gate = nullptr) {
+    int run_stages(uint32_t m, uint32_t dstride, hipStream_t st, const SortExport* borrowed = nullptr, Phase phase = Phase::All, hipEvent_t gate = nullptr) {
         Work& l = ws;
         int rc;
-        const uint32_t seg_len = borrowed ? borrowed->view.seg_len : (phase == 2 ? l.seg_len : pick_seg_len((uint64_t)l.w_count * m));
+        const uint32_t seg_len = borrowed ? borrowed->view.seg_len : (phase == Phase::Rest ? l.seg_len : pick_seg_len((uint64_t)l.w_count * m));
         l.seg_len = seg_len;
-        if (phase == 2) {
-            // sorted in phase 1
+        if (phase == Phase::Rest) {
+            // sorted by the SortOnly half
         } else if (borrowed) {
             ZK_HIP(hipStreamWaitEvent(st, borrowed->sorted_ready, 0));
         } else if ((rc = front.sort(m, dstride, seg_len, l.w_first, l.w_count, l.groups, st))) {
             return rc;
         }
         const SortedView sv = borrowed ? borrowed->view : front.view();
-        if (phase != 2) ZK_HIP(hipEventRecord(l.ev_acc0, st));
-        if (phase == 1) return ZK_OK;
+        if (phase != Phase::Rest) ZK_HIP(hipEventRecord(l.ev_acc0, st));
+        if (phase == Phase::SortOnly) return ZK_OK;
         if (gate) ZK_HIP(hipStreamWaitEvent(st, gate, 0));
-        l.acc_from_accs = gate != nullptr || phase == 2;
+        l.acc_from_accs = gate != nullptr || phase == Phase::Rest;
         if (l.acc_from_accs) ZK_HIP(hipEventRecord(l.ev_accs, st));
         // priority steps (msm_accumulate.hip.h) for a run in one piece that waits for nothing: the two-step, gated and shared forms
         // are what a prover uses to overlap several plans
-        const bool prio_steps = opt.priority_steps && phase == 0 && !gate && !borrowed;
+        const bool prio_steps = opt.priority_steps && phase == Phase::All && !gate && !borrowed;
         if ((rc = stage_accumulate(m, sv, st, prio_steps))) return rc;
         if (borrowed) ZK_HIP(hipEventRecord(borrowed->release, st));  // the lender's buffers are no longer read
         return stage_reduce(st);   // the caller records ev_end
@@ -420,7 +381,7 @@ struct MsmPlan : MsmPlanBase {
 
     int set_option(const char* name, int64_t value) override {
         std::lock_guard<std::mutex> lock(mu);
-        if (q_pending || q_sorted) return fail(ZK_ERR_ARG, "MSM plan has a run in flight: options change between runs");
+        if (in_flight()) return fail(ZK_ERR_ARG, "MSM plan has a run in flight: options change between runs");
         if (!strcmp(name, "segment_lanes")) {
             if (value < 64) return fail(ZK_ERR_ARG, "segment_lanes must be at least 64");
             // the partials buffer was sized for the creation-time target: more lanes than that would overrun it
@@ -449,18 +410,16 @@ struct MsmPlan : MsmPlanBase {
 
     int debug_view(uint64_t* out, int cap) override {
         std::lock_guard<std::mutex> lock(mu);
-        if (q_pending || q_sorted) return fail(ZK_ERR_ARG, "MSM plan has a run in flight: the view is read between runs");
+        if (in_flight()) return fail(ZK_ERR_ARG, "MSM plan has a run in flight: the view is read between runs");
         if (!out || cap < ZK_MSM_VIEW_SLOTS) return fail(ZK_ERR_ARG, "zk_msm_plan_debug_view needs room for ZK_MSM_VIEW_SLOTS values");
-        bool split_acc = false;
-        if constexpr (AccumulateSplit<G>::ON) split_acc = opt.split_pairs < 0 ? AccumulateSplit<G>::DEFAULT : opt.split_pairs != 0;
         const SortedView own = front.view();
         const uint64_t v[ZK_MSM_VIEW_SLOTS] = {
             (uint64_t)(uintptr_t)front.digits_buf(), (uint64_t)(uintptr_t)d_bases, (uint64_t)(uintptr_t)own.sorted, (uint64_t)(uintptr_t)own.bstart,
             (uint64_t)(uintptr_t)own.sstart, (uint64_t)(uintptr_t)own.big_list, (uint64_t)(uintptr_t)own.big_count,
             (uint64_t)(uintptr_t)ws.partials.as(), (uint64_t)(uintptr_t)ws.buckets.as(),
-            n, n_api, (uint64_t)c, (uint64_t)nwin, B, glv ? 1u : 0u, pre ? 1u : 0u, wide ? 1u : 0u, (uint64_t)pw_first, (uint64_t)pw_count,
+            n, n_api, (uint64_t)c, (uint64_t)nwin, shape.B, glv ? 1u : 0u, pre ? 1u : 0u, wide ? 1u : 0u, (uint64_t)pw_first, (uint64_t)pw_count,
             (uint64_t)ws.w_first, (uint64_t)ws.w_count, ws.groups, ws.seg_len, q_m, front.view_dstride,
-            (uint64_t)front.view_route, (uint64_t)front.view_fine_log, front.view_split_fine() ? 1u : 0u, split_acc ? 1u : 0u};
+            (uint64_t)front.view_route, (uint64_t)front.view_fine_log, front.view_split_fine() ? 1u : 0u, split_pairs_on() ? 1u : 0u};
         for (int k = 0; k < ZK_MSM_VIEW_SLOTS; ++k) out[k] = v[k];
         return ZK_OK;
     }
@@ -480,36 +439,53 @@ struct MsmPlan : MsmPlanBase {
     }
 
     // state carried from enqueue() to finish()
+    Run q_state = Run::Idle;
     int q_first = 0, q_count = 0;
     uint32_t q_m = 0;
     hipStream_t q_stream = nullptr;
-    bool q_pending = false;
+    bool in_flight() const { return q_state != Run::Idle; }
 
-    bool q_sorted = false;  // enqueue_sort done, enqueue_rest still to come
+    // The prologue of every run (caller holds mu, arguments checked): one run at a time; a borrower of the previous run's sort may
+    // still be reading the buffers this run overwrites; note the run; scalars from the host go to the device; ev_start.
+    // m = entries per window (0: an empty run puts nothing but the wait on the stream), groups = bucket sets
+    int begin_run(hipStream_t st, int w_first, int w_count, uint32_t m, uint32_t groups, const void* host_scalars = nullptr, size_t scalar_bytes = 0) {
+        if (in_flight()) return fail(ZK_ERR_ARG, "MSM plan already has a run in flight: call zk_msm_plan_finish first");
+        q_first = w_first; q_count = w_count; q_m = m; q_stream = st;
+        if (ws.lent) {
+            ZK_HIP(hipStreamWaitEvent(st, ws.ev_release, 0));
+            ws.lent = false;
+        }
+        if (m == 0) return ZK_OK;
+        if (host_scalars) ZK_HIP(hipMemcpyAsync(front.scalars_buf(), host_scalars, scalar_bytes, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipEventRecord(ev_start, st));
+        ws.w_first = w_first;
+        ws.w_count = w_count;
+        ws.groups = groups;
+        return ZK_OK;
+    }
 
     int enqueue(uint64_t n_scalars, const void* scalars, int on_device, int w_first, int w_count, hipStream_t st) override {
-        return enqueue_phase(n_scalars, scalars, on_device, w_first, w_count, st, 0);
+        return enqueue_phase(n_scalars, scalars, on_device, w_first, w_count, st, Phase::All);
     }
     int enqueue_sort(uint64_t n_scalars, const void* scalars, int on_device, int w_first, int w_count, hipStream_t st) override {
-        return enqueue_phase(n_scalars, scalars, on_device, w_first, w_count, st, 1);
+        return enqueue_phase(n_scalars, scalars, on_device, w_first, w_count, st, Phase::SortOnly);
     }
     hipEvent_t accumulate_done_event() override { return ws.ev_acc1; }
     int enqueue_rest(MsmPlanBase* after) override {
         std::lock_guard<std::mutex> lock(mu);
-        if (!q_sorted) return fail(ZK_ERR_ARG, "zk_msm_plan_enqueue_rest without zk_msm_plan_enqueue_sort");
-        q_sorted = false;
+        if (q_state != Run::Sorted) return fail(ZK_ERR_ARG, "zk_msm_plan_enqueue_rest without zk_msm_plan_enqueue_sort");
+        q_state = Run::Idle;
         if (q_m > 0) {
-            int rc = run_stages(q_m, (q_m + 7u) & ~7u, q_stream, nullptr, 2, after ? after->accumulate_done_event() : nullptr);
+            int rc = run_stages(q_m, (q_m + 7u) & ~7u, q_stream, nullptr, Phase::Rest, after ? after->accumulate_done_event() : nullptr);
             if (rc) return rc;
             ZK_HIP(hipEventRecord(ev_end, q_stream));
         }
-        q_pending = true;
+        q_state = Run::Pending;
         return ZK_OK;
     }
 
-    int enqueue_phase(uint64_t n_scalars, const void* scalars, int on_device, int w_first, int w_count, hipStream_t st, int phase) {
+    int enqueue_phase(uint64_t n_scalars, const void* scalars, int on_device, int w_first, int w_count, hipStream_t st, Phase phase) {
         std::lock_guard<std::mutex> lock(mu);
-        if (q_pending || q_sorted) return fail(ZK_ERR_ARG, "MSM plan already has a run in flight: call zk_msm_plan_finish first");
         if (n_scalars > n_api) return fail(ZK_ERR_LENGTH, "Number of points and scalars mismatch");
         if (w_count <= 0) { w_first = pw_first; w_count = pw_count; }
         if (w_first < pw_first || w_first + w_count > pw_first + pw_count)
@@ -517,42 +493,28 @@ struct MsmPlan : MsmPlanBase {
                                         std::to_string(pw_first + pw_count) + "))");
         const uint32_t m_api = (uint32_t)n_scalars;
         const uint32_t m = glv ? 2 * m_api : m_api;  // entries per window
-        q_first = w_first; q_count = w_count; q_m = m; q_stream = st;
-        if (ws.lent) {  // a borrower of the previous run's sort may still be reading the buffers this run overwrites
-            ZK_HIP(hipStreamWaitEvent(st, ws.ev_release, 0));
-            ws.lent = false;
-        }
+        int rc = begin_run(st, w_first, w_count, m, pre ? 1u : (uint32_t)w_count, on_device ? nullptr : scalars, (size_t)m_api * FrP::W * 4);
+        if (rc) return rc;
         if (m > 0) {
-            const uint32_t* sc = (const uint32_t*)scalars;
-            if (!on_device) {
-                ZK_HIP(hipMemcpyAsync(front.scalars_buf(), scalars, (size_t)m_api * FrP::W * 4, hipMemcpyHostToDevice, st));
-                sc = front.scalars_buf();
-            }
-            const uint32_t dstride = (m + 7u) & ~7u;
-            ZK_HIP(hipEventRecord(ev_start, st));
-            int rc = front.digits(sc, m_api, w_first, w_count, st);  // 1. the windows of this run
-            if (rc) return rc;
-            ws.w_first = w_first;
-            ws.w_count = w_count;
-            ws.groups = pre ? 1u : (uint32_t)w_count;
-            if ((rc = run_stages(m, dstride, st, nullptr, phase))) return rc;
-            if (phase == 0) ZK_HIP(hipEventRecord(ev_end, st));
+            const uint32_t* sc = on_device ? (const uint32_t*)scalars : front.scalars_buf();
+            if ((rc = front.digits(sc, m_api, w_first, w_count, st))) return rc;  // 1. the windows of this run
+            if ((rc = run_stages(m, (m + 7u) & ~7u, st, nullptr, phase))) return rc;
+            if (phase == Phase::All) ZK_HIP(hipEventRecord(ev_end, st));
         }
-        if (phase == 1) q_sorted = true;
-        else q_pending = true;
+        q_state = phase == Phase::SortOnly ? Run::Sorted : Run::Pending;
         return ZK_OK;
     }
 
     int cancel() override {
         std::lock_guard<std::mutex> lock(mu);
-        if ((q_pending || q_sorted) && q_stream) ZK_HIP(hipStreamSynchronize(q_stream));
-        q_pending = q_sorted = false;
+        if (in_flight() && q_stream) ZK_HIP(hipStreamSynchronize(q_stream));
+        q_state = Run::Idle;
         return ZK_OK;
     }
 
     int export_sort(SortExport* out) override {
         std::lock_guard<std::mutex> lock(mu);
-        if ((!q_pending && !q_sorted) || q_m == 0) return fail(ZK_ERR_ARG, "the lending plan has no run in flight");
+        if (!in_flight() || q_m == 0) return fail(ZK_ERR_ARG, "the lending plan has no run in flight");
         out->view = front.view();
         out->view.seg_len = ws.seg_len;
         out->n = n; out->m = q_m; out->groups = ws.groups;
@@ -573,103 +535,37 @@ struct MsmPlan : MsmPlanBase {
         int rc = lender->export_sort(&ex);
         if (rc) return rc;
         std::lock_guard<std::mutex> lock(mu);
-        if (q_pending || q_sorted) return fail(ZK_ERR_ARG, "MSM plan already has a run in flight: call zk_msm_plan_finish first");
         if (ex.n != n || ex.c != c || ex.nwin != nwin || ex.pre != pre || ex.glv != glv || ex.endo != (glv ? G::ENDO_ID : 0) || ex.scalar_bits != FrP::BITS ||
             ex.pw_first != pw_first || ex.pw_count != pw_count)
             return fail(ZK_ERR_ARG, "plans differ in size, window layout or mode: the sort cannot be shared");
-        if (ws.lent) {
-            ZK_HIP(hipStreamWaitEvent(st, ws.ev_release, 0));
-            ws.lent = false;
-        }
-        q_first = ex.w_first; q_count = ex.w_count; q_m = ex.m; q_stream = st;
-        ZK_HIP(hipEventRecord(ev_start, st));
-        ws.w_first = ex.w_first;
-        ws.w_count = ex.w_count;
-        ws.groups = ex.groups;
-        rc = run_stages(ex.m, (ex.m + 7u) & ~7u, st, &ex);
-        if (rc) return rc;
+        if ((rc = begin_run(st, ex.w_first, ex.w_count, ex.m, ex.groups))) return rc;   // ex.m > 0: export_sort lends no empty run
+        if ((rc = run_stages(ex.m, (ex.m + 7u) & ~7u, st, &ex))) return rc;
         ZK_HIP(hipEventRecord(ev_end, st));
-        q_pending = true;
+        q_state = Run::Pending;
         return ZK_OK;
     }
 
     int finish(uint64_t* out) override {
         std::lock_guard<std::mutex> lock(mu);
-        if (q_sorted) return fail(ZK_ERR_ARG, "zk_msm_plan_finish before zk_msm_plan_enqueue_rest");
-        if (!q_pending) return fail(ZK_ERR_ARG, "zk_msm_plan_finish without a pending run");
-        q_pending = false;
-        typedef typename G::HostF HF;  // 64-bit-limb host arithmetic for the sequential tail (host64.hip.h)
-        XYZZ<HF> total = xyzz_inf<HF>();
-        std::chrono::steady_clock::time_point tail_t0;
-        if (q_m > 0) {
-            ZK_HIP(hipEventSynchronize(ev_end));
-            tail_t0 = std::chrono::steady_clock::now();
-            // 8. host tail.  Per bucket set, with row blocks (S_k, T_k), column blocks (S'_k, T'_k), C = 2^lc, WS_BLOCK = 2^7:
-            //        W = 2^(lc+7) X_R + 2^lc sum S_k + 2^7 X_C + (sum S'_k + sum T_k),   X = sum_k k T_k  (k = 1 at most)
-            //    general mode: total = sum_w 2^(c w) W_w by Horner from the top window down; the factors ride along the c
-            //    doublings between two windows, so a set costs c doublings whatever its block structure;
-            //    fixed-base mode: one set, the same chain.
-            int lc = 0;
-            while ((1u << lc) < C) ++lc;
-            const int groups = (int)ws.groups;
-            const uint32_t* rows_fin = h_final;
-            const uint32_t* cols_fin = h_final + (size_t)groups * bpr * 2 * XW;
-            auto pt = [](const uint32_t* p) { return HF::xyzz_from_device(p); };
-            bool first_set = true;
-            for (int g = groups - 1; g >= 0; --g) {
-                // X = sum_k k T_k as a running sum of suffixes (from the top block down): two additions per block
-                XYZZ<HF> sum_s = xyzz_inf<HF>(), sum_t = xyzz_inf<HF>(), x_r = xyzz_inf<HF>();
-                for (int k = (int)bpr - 1; k >= 0; --k) {
-                    const uint32_t* q = rows_fin + ((size_t)g * bpr + k) * 2 * XW;
-                    sum_s = xyzz_add<HF>(sum_s, pt(q));
-                    if (k > 0) {
-                        sum_t = xyzz_add<HF>(sum_t, pt(q + XW));  // T_k + .. + T_top
-                        x_r = xyzz_add<HF>(x_r, sum_t);
-                    } else {
-                        sum_t = xyzz_add<HF>(sum_t, pt(q + XW));
-                    }
-                }
-                XYZZ<HF> sum_sc = xyzz_inf<HF>(), x_c = xyzz_inf<HF>(), suf_c = xyzz_inf<HF>();
-                for (int k = (int)bpc - 1; k >= 0; --k) {
-                    const uint32_t* q = cols_fin + ((size_t)g * bpc + k) * 2 * XW;
-                    sum_sc = xyzz_add<HF>(sum_sc, pt(q));
-                    if (k > 0) {
-                        suf_c = xyzz_add<HF>(suf_c, pt(q + XW));
-                        x_c = xyzz_add<HF>(x_c, suf_c);
-                    }
-                }
-                // terms in descending order of their exponent; `at` = exponent the accumulator currently sits at
-                int at = first_set ? -1 : c;
-                auto step = [&](int exp, const XYZZ<HF>& term, bool present) {
-                    if (!present) return;
-                    if (at >= 0) for (int k = 0; k < at - exp; ++k) total = xyzz_dbl<HF>(total);
-                    total = xyzz_add<HF>(total, term);
-                    at = exp;
-                };
-                if (bpr > 1 && lc + WS_BLOCK_LOG > c && !first_set) return fail(ZK_ERR_ARG, "internal: reduction layout does not fit the window");
-                step(lc + WS_BLOCK_LOG, x_r, bpr > 1);
-                step(lc, sum_s, true);
-                step(WS_BLOCK_LOG, x_c, bpc > 1);
-                step(0, xyzz_add<HF>(sum_sc, sum_t), true);
-                first_set = false;
-            }
-            if (!pre) for (int k = 0; k < c * q_first; ++k) total = xyzz_dbl<HF>(total);
-            float sort_ms = 0, acc_ms = 0, red_ms = 0, t = 0;
-            if (hipEventElapsedTime(&t, ev_start, ws.ev_acc0) == hipSuccess) sort_ms += t;
-            if (hipEventElapsedTime(&t, ws.acc_from_accs ? ws.ev_accs : ws.ev_acc0, ws.ev_acc1) == hipSuccess) acc_ms += t;
-            if (hipEventElapsedTime(&t, ws.ev_acc1, ev_end) == hipSuccess) red_ms += t;
-            timings[0] = sort_ms;   // digits + sort
-            timings[1] = acc_ms;    // accumulate kernel
-            timings[2] = red_ms;    // combine + reduction + D2H
-        }
-        HF::affine_to_canonical(xyzz_to_affine<HF>(total), out);
-        if (q_m > 0) {
-            // the tail runs on the host: its time comes from the host's clock (an event recorded and awaited here would put a
-            // GPU round trip of 10-20 us on the critical path of every MSM just to time it)
-            timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tail_t0).count();
+        if (q_state == Run::Sorted) return fail(ZK_ERR_ARG, "zk_msm_plan_finish before zk_msm_plan_enqueue_rest");
+        if (q_state != Run::Pending) return fail(ZK_ERR_ARG, "zk_msm_plan_finish without a pending run");
+        q_state = Run::Idle;
+        if (q_m > 0) ZK_HIP(hipEventSynchronize(ev_end));
+        // 8. the tail runs on the host: its time comes from the host's clock (an event recorded and awaited here would put a
+        // GPU round trip of 10-20 us on the critical path of every MSM just to time it)
+        const auto tail_t0 = std::chrono::steady_clock::now();
+        int rc = msm_host_tail<G>(h_final, q_m > 0 ? ws.groups : 0u, shape, c, q_first, pre, out);   // no bucket set: the empty MSM, infinity
+        if (rc || q_m == 0) return rc;
+        timings[3] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tail_t0).count();
+        auto elapsed = [](hipEvent_t from, hipEvent_t to) {
             float t = 0;
-            timings[4] = hipEventElapsedTime(&t, ev_start, ev_end) == hipSuccess ? t + timings[3] : 0.0f;
-        }
+            return hipEventElapsedTime(&t, from, to) == hipSuccess ? t : 0.0f;
+        };
+        timings[0] = elapsed(ev_start, ws.ev_acc0);                                     // digits + sort
+        timings[1] = elapsed(ws.acc_from_accs ? ws.ev_accs : ws.ev_acc0, ws.ev_acc1);   // accumulate kernel
+        timings[2] = elapsed(ws.ev_acc1, ev_end);                                       // combine + reduction + D2H
+        float t = 0;
+        timings[4] = hipEventElapsedTime(&t, ev_start, ev_end) == hipSuccess ? t + timings[3] : 0.0f;
         return ZK_OK;
     }
 };

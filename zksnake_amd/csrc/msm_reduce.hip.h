@@ -2,6 +2,7 @@
 // reduction sum_b (b + 1) B_b on lane pairs (pair.hip.h).  Pipeline overview: msm_impl.hip.h.
 #pragma once
 #include "msm_common.hip.h"
+#include "msm_reduce_plan.h"
 
 namespace zkmi {
 
@@ -81,16 +82,9 @@ __global__ __launch_bounds__(COMBINE_THREADS) void combine_kernel(const uint32_t
 // Both kernels hold a point as a lane pair (pair.hip.h): an addition is seven multiplications deep instead of
 // fourteen and a half, which is what these latency-bound stages are made of.
 
-// Two strided sums in one launch (rows and columns run side by side):
+// Two strided sums in one launch (rows and columns run side by side), each a SumJob (msm_reduce_plan.h):
 //   out[o] = sum_{j < count} in[(o / per_group) * group_stride + (o % per_group) * outer + j * inner]
 // lpo lanes = lpo / 2 pairs per output element; the pairs stride over j, then a shuffle tree over the pairs.
-struct SumJob {
-    uint32_t n_out, per_group, group_stride, outer, inner, count;
-    uint32_t out_offset;  // in points, into the shared output array
-    uint32_t split = 1, outer2 = 0;  // the index x inside a group is taken apart: (x / split) * outer + (x % split) * outer2
-    uint32_t in_offset = 0;          // in points, into the input array
-};
-
 template <class G>
 __global__ __launch_bounds__(256) void strided_sum_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                           SumJob j0, SumJob j1, uint32_t lpo) {
@@ -133,9 +127,7 @@ __global__ __launch_bounds__(256) void strided_sum_kernel(const uint32_t* __rest
 // (log m steps) followed by a tree sum of the suffixes 1..m-1.  n0 arrays of m0 points from in0, then arrays of m1
 // points from in1; block k of an array covers its points [k WS_BLOCK, ..) with LOCAL weights 0, 1, ..: the host tail adds
 // k WS_BLOCK T_k along its Horner chain, where those doublings cost nothing extra.  out: (S, T) per block, arrays of
-// in0 first.  Dynamic LDS: HalfRegs<F>::COUNT words per lane, word-major.
-constexpr int WS_BLOCK = 128;
-constexpr int WS_BLOCK_LOG = 7;
+// in0 first.  Dynamic LDS: HalfRegs<F>::COUNT words per lane, word-major.  WS_BLOCK: msm_reduce_plan.h.
 constexpr int HS_THREADS = 2 * WS_BLOCK;
 template <class G>
 __global__ __launch_bounds__(HS_THREADS) void weighted_sum_kernel(const uint32_t* __restrict__ in0, uint32_t m0, uint32_t n0,
@@ -178,6 +170,39 @@ __global__ __launch_bounds__(HS_THREADS) void weighted_sum_kernel(const uint32_t
         __syncthreads();
     }
     if (pj == 0) half_store<F>(out + (size_t)blockIdx.x * 2 * XW, odd, v);  // S
+}
+
+// ---- host: one launcher per kernel ------------------------------------------------------------------------------------
+// The only copy of each kernel's grid / block / dynamic-LDS expression: MsmPlan (msm_impl.hip.h) and the stage harness
+// (tests/native/reduce_stages.hip) launch through these.  Errors are the caller's to collect (hipGetLastError).
+
+template <class G>
+inline void launch_combine(const uint32_t* partials, const uint32_t* run_start, uint32_t n_keys, const uint32_t* big_list,
+                           const uint32_t* big_count, uint32_t* buckets, hipStream_t st) {
+    const uint32_t small_blocks = (2 * n_keys + COMBINE_THREADS - 1) / COMBINE_THREADS;
+    hipLaunchKernelGGL(combine_kernel<G>, dim3(small_blocks + COMBINE_WAVE_BLOCKS + COMBINE_BIG_BLOCKS), dim3(COMBINE_THREADS), 0, st,
+                       partials, run_start, n_keys, small_blocks, big_list, big_count, buckets);
+}
+
+template <class G>
+inline void launch_strided_sum(const uint32_t* in, uint32_t* out, const SumJob& j0, const SumJob& j1, uint32_t lpo, hipStream_t st) {
+    hipLaunchKernelGGL(strided_sum_kernel<G>, dim3((unsigned)((((uint64_t)j0.n_out + j1.n_out) * lpo + 255) / 256)), dim3(256), 0, st,
+                       in, out, j0, j1, lpo);
+}
+
+// LDS above 64 KiB needs the opt-in: once per process, before the first launch_weighted_sum of the group
+template <class G>
+inline hipError_t weighted_sum_set_attributes() {
+    return hipFuncSetAttribute((const void*)weighted_sum_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(HalfRegs<typename G::F>::COUNT * HS_THREADS * 4));
+}
+
+// n0 arrays of m0 points from in0 and n0 arrays of m1 points from in1: one workgroup per block of WS_BLOCK points
+template <class G>
+inline void launch_weighted_sum(const uint32_t* in0, uint32_t m0, uint32_t n0, const uint32_t* in1, uint32_t m1, uint32_t* out, hipStream_t st) {
+    const uint32_t blocks = n0 * ((m0 + WS_BLOCK - 1) / WS_BLOCK + (m1 + WS_BLOCK - 1) / WS_BLOCK);
+    hipLaunchKernelGGL(weighted_sum_kernel<G>, dim3(blocks), dim3(HS_THREADS), (size_t)HalfRegs<typename G::F>::COUNT * HS_THREADS * 4, st,
+                       in0, m0, n0, in1, m1, out);
 }
 
 }  // namespace zkmi
