@@ -543,6 +543,24 @@ int zk_pcs_round_dev(int curve, int log_n, int k, void* d_c, void* d_s, const ui
  * Enqueues only. */
 int zk_pcs_verify_scalars_dev(int curve, int log_n, const uint64_t* u, const uint64_t* c, void* d_out, void* stream);
 
+/* ---- multilinear KZG commitment, scalar side of an opening (csrc/mlpcs.hip) ------------------------------------------------
+ * PST13 multilinear KZG as in arkworks' MultilinearPC, over the tables of csrc/mle.hip (variable 0 is the least significant bit of
+ * the index, point[i] goes to variable i).  Opening f at z is the chain, from f_0 = f and for k = 0 .. log_n-1,
+ *     q_k[b] = f_k[2b+1] - f_k[2b],     f_(k+1)[b] = f_k[2b] + z_k q_k[b],
+ * so that f(x) - f(z) = sum_k (x_k - z_k) q_k(x_(k+1), ..) and f_(log_n)[0] = f(z): the q_k are the scalars of the proof's log_n
+ * MSMs and the evaluation comes out of the same pass.  0 <= log_n <= ZK_MLPCS_MAX_LOG (the commitment scheme's cap: its SRS holds
+ * 2^(log_n + 1) points).  Tiled like zk_mle_fix_dev: ceil(log_n / ZK_MLE_TILE_LOG) launches, each on a table 2^ZK_MLE_TILE_LOG
+ * times smaller; every quotient is written once. */
+#define ZK_MLPCS_MAX_LOG 24
+/* d_f: 2^log_n canonical Fr elements, left unchanged.  point: log_n * 4 limbs (host; may be NULL when log_n = 0), reduced on
+ * entry when >= r.  d_q receives all 2^log_n - 1 quotient entries (canonical), level 0 first: level k has 2^(log_n-1-k) entries and
+ * starts at element 2^log_n - 2^(log_n-k).  eval_out (4 limbs, host) = f(point).  d_work: device scratch of at least
+ * 2^(max(log_n - ZK_MLE_TILE_LOG, 0) + 1) elements, or NULL to use library memory (the zk_mle_eval_dev convention).  log_n = 0
+ * writes no quotient (d_q may be NULL) and returns f[0].  ZK_ERR_ARG, with nothing written, for a null pointer, log_n out of
+ * range, an unknown curve, d_q overlapping d_f, or d_work overlapping either; ZK_ERR_HIP without a GPU.  Synchronises the stream. */
+int zk_mlpcs_quotients_dev(int curve, int log_n, const void* d_f, const uint64_t* point, void* d_q, uint64_t* eval_out, void* d_work,
+                           void* stream);
+
 /* ---- Merkle vector commitment: BLAKE2b leaves, tree and opening paths (csrc/merkle.hip) ----------------------------------
  * The hashing of commitment/vector/merkle.py with alg = "blake2b": BLAKE2b-512 without key, salt or personalisation (RFC 7693,
  * what hashlib.new("blake2b", data) computes), one digest per lane.  A tree over n leaves is its levels one after the other in

@@ -40,6 +40,7 @@ MSM_ROUTE_RANGED, MSM_ROUTE_ONE_LEVEL, MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO
 MSM_ROUTES_TWO_LEVEL = (MSM_ROUTE_TWO_LEVEL_DERIVE, MSM_ROUTE_TWO_LEVEL_SCAN, MSM_ROUTE_TWO_LEVEL_PARTIAL)
 IPA_MAX_LOG = 22  # ZK_IPA_MAX_LOG: an inner-product argument has at most 2^22 elements per vector
 PCS_MAX_LOG = 21  # ZK_PCS_MAX_LOG: an inner-product polynomial commitment has at most 2^21 coefficients
+MLPCS_MAX_LOG = 24  # ZK_MLPCS_MAX_LOG: a multilinear KZG commitment has at most 24 variables
 MLE_TILE_LOG = 8  # ZK_MLE_TILE_LOG: variables one launch of the multilinear kernels folds per 256-element tile
 MERKLE_DIGEST = 64  # ZK_MERKLE_DIGEST: bytes per BLAKE2b-512 digest, and per node of a Merkle tree
 MERKLE_MAX_LOG = 26  # ZK_MERKLE_MAX_LOG: a Merkle tree has at most 2^26 leaves
@@ -149,6 +150,7 @@ SIGNATURES = {
     "zk_rp_verify_scalars_dev": (_i, [_i, _i, _i, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
     "zk_pcs_round_dev": (_i, [_i, _i, _i, _vp, _vp, _u64p, _u64p, _u64p, _vp, _vp, _u64p, _vp]),
     "zk_pcs_verify_scalars_dev": (_i, [_i, _i, _u64p, _u64p, _vp, _vp]),
+    "zk_mlpcs_quotients_dev": (_i, [_i, _i, _vp, _u64p, _vp, _u64p, _vp, _vp]),
     "zk_blake2b_rows_dev": (_i, [_u64, _vp, _u64, _vp, _vp]),
     "zk_blake2b_items_dev": (_i, [_u64, _vp, _u64, _vp, _vp, _vp]),
     "zk_merkle_layout": (_i, [_u64, ctypes.POINTER(_i), _u64p, _u64p]),

@@ -14,7 +14,7 @@
 // variables there, so fixing k variables reads the table once per MLE_TILE_LOG variables instead of k times.
 #include <algorithm>
 #include <vector>
-#include "fr_sum.hip.h"
+#include "mle_fold.hip.h"
 
 namespace zkmi {
 using mem::DevBuf;
@@ -26,12 +26,7 @@ constexpr unsigned MLE_MAX_PARTIALS = 1024;
 static_assert(MLE_MAX_PARTIALS == FR_MAX_BLOCKS, "the sizes of tests/test_gpu_fr_large.py sit on the shared cap");
 constexpr int SC_MAX_TABLES = 8, SC_MAX_TERMS = 8, SC_MAX_DEG = 3;
 
-// ---- fix_variables ---------------------------------------------------------------------------------------
-template <class P>
-struct FixArgs {
-    Fp<P> r_m[MLE_TILE_LOG];  // r R: mont(d, r R) = r d
-};
-
+// ---- fix_variables (FixArgs, fold_step and fix_work_elems: mle_fold.hip.h, shared with mlpcs.hip) -------------
 // n input elements (a power of two), f >= 1 variables folded per tile of min(n, MLE_TILE) elements; (tile >> f) survivors per tile
 template <class P>
 __global__ __launch_bounds__(MLE_TILE) void mle_fix_kernel(uint64_t n, int f, FixArgs<P> a, const uint32_t* __restrict__ in,
@@ -46,7 +41,7 @@ __global__ __launch_bounds__(MLE_TILE) void mle_fix_kernel(uint64_t n, int f, Fi
         const int half = MLE_TILE >> (s + 1);
         if (t < half) {
             const Fp<P> lo = lds_get<P>(lds, 2 * t), hi = lds_get<P>(lds, 2 * t + 1);
-            res = fp_add<P>(lo, fp_mul<P>(fp_sub<P>(hi, lo), a.r_m[s]));
+            res = fold_step<P>(lo, fp_sub<P>(hi, lo), a.r_m[s]);
         }
         if (s + 1 == f) break;  // the last level goes straight to memory
         __syncthreads();
@@ -172,13 +167,6 @@ __global__ __launch_bounds__(MLE_TILE) void sumcheck_round_kernel(uint64_t pairs
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-// device elements a chain of fix passes needs between its first and its last pass
-static uint64_t fix_work_elems(int log_n, int k) {
-    const int passes = (k + MLE_TILE_LOG - 1) / MLE_TILE_LOG;
-    if (passes < 2) return 0;
-    return (1ull << (log_n - MLE_TILE_LOG)) + (passes > 2 ? 1ull << (log_n - 2 * MLE_TILE_LOG) : 0);
-}
-
 // in (2^log_n) -> out (2^(log_n - k)), variables 0 .. k-1 fixed; `work` holds fix_work_elems(log_n, k) elements.  Enqueues only.
 template <class P>
 static int fix_chain(int log_n, const uint32_t* in, int k, const uint64_t* r, uint32_t* out, uint32_t* work, hipStream_t st) {
@@ -191,9 +179,7 @@ static int fix_chain(int log_n, const uint32_t* in, int k, const uint64_t* r, ui
     int cur_log = log_n, done = 0;
     for (int pass = 0; done < k; ++pass) {
         const int f = std::min(MLE_TILE_LOG, k - done);
-        FixArgs<P> a;
-        for (int s = 0; s < MLE_TILE_LOG; ++s)
-            a.r_m[s] = s < f ? fr_mont<P>(r + 4 * (done + s)) : fp_zero<P>();
+        const FixArgs<P> a = fix_args<P>(r + 4 * done, f);
         uint32_t* dst = done + f == k ? out : tmp[pass & 1];
         const uint64_t n = 1ull << cur_log;
         hipLaunchKernelGGL(mle_fix_kernel<P>, dim3((unsigned)((n + MLE_TILE - 1) / MLE_TILE)), dim3(MLE_TILE), 0, st, n, f, a, cur, dst);
