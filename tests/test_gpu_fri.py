@@ -1,7 +1,15 @@
 """GPU: the FRI polynomial commitment end to end.  Commitments, values and whole proofs equal the integer model's
 (tests/fri_model.py) with ==, the bytes equal the golden file, an oracle is reused without a second extension, the four input
 kinds agree, and at 2^16 coefficients the proof verifies, a wrong value does not, and the root is hashlib's over the downloaded
-pair-order evaluations."""
+pair-order evaluations.
+
+One run above the capped grid of 2^18 threads is tied to the CPU oracle: 2^18 uniform coefficients at blowup 4, 64 queries and 16
+final coefficients, the benchmark's shape at the smallest size (N = 2^20) at which both the scale pass and the permutation of
+the extension take a second item per thread.  The committed evaluations equal, in whole, the oracle's transform of c[i] g^i
+(tests/test_gpu_fri_kernels.py builds it, spot-checked by Horner's rule), the root is hashlib's over those 2^19 leaves, the
+opened value is Horner's, and the host verifier accepts the proof and refuses a changed value, another polynomial's root and a
+flipped byte in the first queried leaf; the folds from 2^20 values down to 64 and the final coefficients so run on layers
+derived from checked data."""
 
 import hashlib
 import json
@@ -12,7 +20,9 @@ import numpy as np
 import pytest
 
 import fri_model as M
+import merkle_model
 from test_fri_model import multi_case, rand_point, rand_poly
+from test_gpu_fri_kernels import lde_reference
 from zksnake_amd import _native as N
 from zksnake_amd.commitment.polynomial import FRI, FriOracle, FriProof, MultiOpeningQuery
 from zksnake_amd.frvec import DevVec, FrOps
@@ -131,6 +141,37 @@ def test_two_to_the_sixteen(gpu, curve):
     while len(level) > 1:
         level = [hashlib.blake2b(level[i] + level[i + 1]).digest() for i in range(0, len(level), 2)]
     assert level[0] == oracle.root == fri.commit(vec)
+    oracle.release()
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_above_one_grid_against_the_oracle(gpu, curve):
+    """the benchmark's shape at 2^18 coefficients: N = 2^20, see the module docstring"""
+    fri = FRI(1 << 18, curve, blowup=4, queries=64, final=16)
+    fri.setup()
+    r = fri.order
+    ref = lde_reference(curve, "commit-2^20")
+    assert ref.size == fri.size == 1 << 20 and ref.shift == fri.shift and len(ref.coeffs) == fri.n
+    oracle = fri.oracle(ref.limbs)
+    assert (oracle.evals.download() == ref.pairs).all(), "the committed evaluations differ from the oracle's transform"
+    leaves = [hashlib.blake2b(ref.pairs[j:j + 2].tobytes()).digest() for j in range(0, fri.size, 2)]
+    assert len(leaves) == 1 << 19 and oracle.root == merkle_model.levels(leaves)[-1][0]
+    z = 0x1234567
+    assert not fri._in_domain(z)
+    proof, value = fri.open(oracle, z)
+    assert value == M.poly_eval(ref.coeffs, z, r)
+    assert len(proof.roots) == 13 and len(proof.final) == 16 and len(proof.queries) == 64
+    assert fri.verify(oracle.root, proof, z, value)
+    assert not fri.verify(oracle.root, proof, z, (value + 1) % r)
+    second = ref.limbs.copy()
+    second[5] = ref.limbs[6]
+    other_root = fri.commit(second)
+    assert other_root != oracle.root and not fri.verify(other_root, proof, z, value)
+    bad = FriProof.from_bytes(proof.to_bytes())
+    assert bad == proof and fri.verify(oracle.root, bad, z, value)
+    leaf, path = bad.queries[0][0][0]
+    bad.queries[0][0][0] = (bytes([leaf[0] ^ 1]) + leaf[1:], path)
+    assert not fri.verify(oracle.root, bad, z, value)
     oracle.release()
 
 

@@ -2,9 +2,30 @@
 with ==: the fold at every small size in full, at one and two workgroups, and at the first size where a thread takes a second
 grid-stride item (closed form on a degree-3 polynomial); the low-degree extension against Horner's rule; the row gather on
 repeated, first, last and out-of-range indices; and each of them on a busy stream, in the manner of
-tests/test_gpu_stream_state_protocols.py."""
+tests/test_gpu_stream_state_protocols.py.
+
+The extension at and past the capped grid of 2^18 threads (1024 workgroups of 256), whole d_out and whole d_work against the CPU
+oracle's transform of c[i] shift^i (a running product in Python integers), the reference itself spot-checked by Horner's rule.
+Coefficients are uniform below r, with 0 and r - 1 at index 0, at 2^18 - 1, at 2^18 and at the last coefficient, and nonzero
+elements lie behind the coefficients in device memory, which a loose guard would read.  One test item per field and size:
+  N = 2^18, 2^17 - 3 coefficients   the largest size with one item per thread: a thread's seed power uses all 18 squarings, and the
+                                    transform under the scale pass is a multi-pass one;
+  N = 2^19, 2^18 coefficients       the first second item of the scale pass, stepped by shift^(2^18) for a random full-width
+                                    shift; every second item is padding and must be written as zero (so the stepped
+                                    power itself multiplies nothing here: the two sizes below are the ones that see it);
+  N = 2^20, 2^18 + 5 coefficients   second items that hold a coefficient for threads 0..4 only, so the guard i < n_coeffs acts
+                                    inside a second item; the first second trip of the permutation (N/2 = 2^19 pairs);
+  N = 2^20, 2^19 - 1 coefficients   every second item but the last holds a coefficient.
+(2^18 coefficients at blowup 4, N = 2^20, is the reference of tests/test_gpu_fri.py's end-to-end run and is built here too.)
+
+The row gather past one grid and at both ends of row_bytes, with out-of-range indices, the first, the last and a repeated row
+among the first eight and the last eight queries (the last ones are those a second item serves):
+  row_bytes = 64, 300 rows, k = 2^16 + 1        2^18 + 4 chunks: threads 0..3 take a second item;
+  row_bytes = 16, 1 and 5 rows, k = 2^18 + 3    the smallest row, one chunk per row, three second items;
+  row_bytes = 65536, 3 rows, k = 65             the largest row: 266 240 chunks, e / chunks divides by 4096."""
 
 import random
+from collections import namedtuple
 
 import numpy as np
 import pytest
@@ -126,6 +147,82 @@ def test_lde_equals_the_model_past_one_workgroup(gpu, curve, cid):
     assert read(d_out, P.N) == M.lde(P, coeffs)
 
 
+# ---- the extension at and past one grid -----------------------------------------------------------------------------------
+
+EDGE = 1 << 18   # threads of the capped grid: the stride of a second item
+# case: (log_n, log_b, coefficients, seed of a random shift or None for the field's generator)
+LDE_CASES = {
+    "one-item-2^18": (17, 1, (1 << 17) - 3, None),
+    "padding-2^19": (18, 1, EDGE, 139),
+    "guard-2^20": (19, 1, EDGE + 5, None),
+    "full-2^20": (19, 1, (1 << 19) - 1, None),
+    "commit-2^20": (18, 2, EDGE, None),   # tests/test_gpu_fri.py
+}
+LdeReference = namedtuple("LdeReference", "size shift coeffs limbs natural pairs")
+_LDE_REFERENCES = {}   # (curve, case) -> LdeReference, built once and read-only
+
+
+def lde_reference(curve, case):
+    """the extension of the case's polynomial from Python integers and the CPU oracle's transform; nothing of csrc/fri.hip"""
+    if (curve, case) in _LDE_REFERENCES:
+        return _LDE_REFERENCES[curve, case]
+    log_n, log_b, count, shift_seed = LDE_CASES[case]
+    cid = M.CURVES[curve][0]
+    cv, r = field(curve)
+    size = 1 << (log_n + log_b)
+    h = size // 2
+    shift = cv.fr_gen if shift_seed is None else vals(r, 3, shift_seed)[0]
+    assert shift % r not in (0, 1) and pow(shift, EDGE, r) != 1, "a step of 1 would hide a wrong step"
+    coeffs = vals(r, count, 130 + list(LDE_CASES).index(case))
+    marks = sorted(i for i in {0, EDGE - 1, EDGE, count - 1} if i < count)
+    for pos, i in enumerate(reversed(marks)):   # the last coefficient is r - 1: nonzero, so a guard one short shows
+        coeffs[i] = 0 if pos % 2 else r - 1
+    scaled, t = [0] * count, 1
+    for i, c in enumerate(coeffs):
+        scaled[i] = c * t % r
+        t = t * shift % r
+    padded = np.zeros((size, 4), dtype=np.uint64)
+    padded[:count] = L(scaled)
+    natural = corc.ntt(cid, padded, threads=8)
+    w = cv.root_of_unity(size)
+    for i in (0, 1, h - 1, h, size - 1):
+        assert I(natural[i:i + 1])[0] == M.poly_eval(coeffs, shift * pow(w, i, r) % r, r), f"the reference is wrong at {i}"
+    pairs = np.empty_like(natural)
+    pairs[0::2], pairs[1::2] = natural[:h], natural[h:]
+    limbs = L(coeffs)
+    for a in (limbs, natural, pairs):
+        a.setflags(write=False)
+    _LDE_REFERENCES[curve, case] = LdeReference(size, shift, coeffs, limbs, natural, pairs)
+    return _LDE_REFERENCES[curve, case]
+
+
+def same_limbs(got, want, what):
+    diff = np.flatnonzero((got != want).any(axis=1))
+    assert diff.size == 0, f"{what}: {diff.size} of {want.shape[0]} elements differ, the first at {diff[0]} (2^18 = {EDGE})"
+
+
+@pytest.mark.parametrize("case", [c for c in LDE_CASES if c != "commit-2^20"])
+@per_field
+def test_lde_at_and_past_one_grid(gpu, curve, cid, case):
+    """whole d_out (pair order) and whole d_work (natural order) against the oracle's transform; eight nonzero elements lie behind
+    the coefficients, d_out is one element longer than the extension and that element keeps its pre-fill"""
+    log_n, log_b, count, _ = LDE_CASES[case]
+    r = field(curve)[1]
+    ref = lde_reference(curve, case)
+    size = ref.size
+    behind = L([r - 1 - i for i in range(8)])
+    held = np.concatenate([ref.limbs, behind])
+    d_coeffs = DeviceBuffer.from_numpy(held)
+    d_work = DeviceBuffer.from_numpy(np.full((size, 4), 9, dtype=np.uint64))
+    d_out = DeviceBuffer.from_numpy(np.full((size + 1, 4), 9, dtype=np.uint64))
+    N.check(gpu.zk_fri_lde_dev(cid, log_n, log_b, count, d_coeffs.ptr, one(ref.shift), d_work.ptr, d_out.ptr, None))
+    got = d_out.download((size + 1, 4))
+    same_limbs(got[:size], ref.pairs, "d_out")
+    assert (got[size] == 9).all(), "the element behind d_out was written"
+    same_limbs(d_work.download((size, 4)), ref.natural, "d_work")
+    assert (d_coeffs.download(held.shape) == held).all(), "the extension wrote to its coefficients"
+
+
 # ---- row gather -----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("row_bytes", [64, 48])
@@ -147,6 +244,31 @@ def test_rows(gpu, k, row_bytes):
     want = rows[np.minimum(idx, np.uint64(n_rows - 1)).astype(np.int64)]
     assert (got[:k] == want).all() and (got[k] == 0xEE).all()
     assert (d_rows.download((n_rows, row_bytes), np.uint8) == rows).all()
+
+
+@pytest.mark.parametrize("row_bytes,rows_of,k", [(64, (300,), (1 << 16) + 1), (16, (1, 5), EDGE + 3), (65536, (3,), 65)],
+                         ids=["64-bytes", "16-bytes", "65536-bytes"])
+def test_rows_past_one_grid(gpu, row_bytes, rows_of, k):
+    """k * chunks > 2^18: the last query (the last three at 16 bytes) is served by a thread's second item and is not row 0"""
+    chunks = row_bytes // 16
+    assert EDGE < k * chunks <= EDGE + 8 * chunks
+    for n_rows in rows_of:
+        rng = np.random.default_rng(95 + n_rows + row_bytes)
+        rows = rng.integers(0, 256, size=(n_rows, row_bytes), dtype=np.uint8)
+        idx = rng.integers(0, n_rows, size=k, dtype=np.uint64)
+        last, mid = n_rows - 1, n_rows // 2
+        idx[:8] = [0, last, mid, mid, mid, n_rows, 1 << 63, 0]      # first, last, repeated, two out of range
+        idx[-8:] = [0, mid, mid, 0, n_rows, 1 << 63, mid, last]
+        fill = np.full((k + 1, row_bytes), 0xEE, dtype=np.uint8)
+        d_rows, d_out, d_idx = DeviceBuffer.from_numpy(rows), DeviceBuffer.from_numpy(fill), DeviceBuffer.from_numpy(idx)
+        N.check(gpu.zk_fri_rows_dev(n_rows, row_bytes, d_rows.ptr, k, d_idx.ptr, d_out.ptr, None))
+        got = d_out.download((k + 1, row_bytes), np.uint8)
+        want = rows[np.minimum(idx, np.uint64(n_rows - 1)).astype(np.int64)]
+        wrong = np.flatnonzero((got[:k] != want).any(axis=1))
+        assert wrong.size == 0, f"{n_rows} rows: {wrong.size} of {k} queries differ, the first is query {wrong[0]}"
+        assert (got[k] == 0xEE).all(), f"{n_rows} rows: the row behind the output was written"
+        assert (d_rows.download((n_rows, row_bytes), np.uint8) == rows).all(), f"{n_rows} rows: the gather wrote to its rows"
+        assert (d_idx.download((k,)) == idx).all()
 
 
 # ---- on a busy stream -----------------------------------------------------------------------------------------------------

@@ -1,5 +1,11 @@
 """GPU: the kernels of csrc/merkle.hip through the C ABI against the hashlib model (tests/merkle_model.py), compared with == on
-bytes.  Outputs are pre-filled with 0xA5 and followed by a guard region that must still hold 0xA5 afterwards."""
+bytes.  Outputs are pre-filled with 0xA5 and followed by a guard region that must still hold 0xA5 afterwards.
+
+Sizes past one workgroup and past the capped grid (GRID = 2^18 threads, 1024 workgroups of 256): the row hasher at GRID + 5 rows
+and the tree at 2 GRID + 3 leaves (the first sizes at which a thread takes a second row, a second parent), the paths at
+2^18 + 4 entries, and the item hasher at 600 items (three workgroups, the first case past one) and at GRID + 5 items, whose
+lengths cycle through aligned and unaligned starts inside every wave and whose five second items are 129 to 300 bytes long,
+once hashed in full and once with the last two offsets beyond data_bytes, so that the clamp acts in a second item."""
 
 import random
 
@@ -115,6 +121,50 @@ def test_items_offsets_past_the_data_are_clamped(gpu):
     assert want == M.H(raw[:500]) + M.H(raw[500:2000]) + M.H(b"") * 2
     assert want != b"".join(M.H(raw[a:b]) for a, b in zip(offsets, offsets[1:]))
     assert run_items(gpu, data, offsets, data_bytes) == want
+
+
+ITEM_PATTERN = (0, 1, 7, 8, 9, 16, 33, 64, 0, 24)   # 162 bytes a cycle: the starts drift through every residue mod 8
+ITEM_TAIL = (129, 256, 3, 200, 300)                 # items GRID .. GRID + 4, the second items of threads 0 .. 4
+
+
+@pytest.fixture(scope="module")
+def many_items():
+    """(data, offsets, digests) of GRID + 5 items: hashlib over every item in full, computed once"""
+    lens = [ITEM_PATTERN[i % len(ITEM_PATTERN)] for i in range(GRID)] + list(ITEM_TAIL)
+    offsets = np.concatenate([[0], np.cumsum(lens)]).tolist()
+    data = rand_bytes(offsets[-1], 19)
+    raw = data.tobytes()
+    starts = {offsets[i] % 8 for i in range(64)}
+    assert 0 in starts and len(starts) > 4, "aligned and unaligned starts inside one wave"
+    assert offsets[GRID] % 8 and offsets[GRID + 1] % 8 and offsets[GRID + 3] % 8 == 0 and offsets[GRID + 4] % 8 == 0
+    return data, offsets, [M.H(raw[a:b]) for a, b in zip(offsets, offsets[1:])]
+
+
+def test_items_past_one_workgroup(gpu, many_items):
+    """600 items: three workgroups, the last one partly idle"""
+    data, offsets, digests = many_items
+    assert run_items(gpu, data[:offsets[600]], offsets[:601], offsets[600]) == b"".join(digests[:600])
+
+
+def test_items_past_one_grid(gpu, many_items):
+    """GRID + 5 items of about 4 MB: threads 0 .. 4 take a second item, of 129 and 256 bytes from starts that are no multiple of
+    8 and of 200 and 300 bytes from starts that are.  With data_bytes at the end of the allocation every item is hashed in full;
+    with data_bytes 77 bytes into item GRID + 3 the last two offsets lie beyond it, inside the same allocation, and the clamp
+    acts in two second items: item GRID + 3 is its first 77 bytes and item GRID + 4 is empty."""
+    data, offsets, digests = many_items
+    n = GRID + 5
+    assert len(digests) == n and 4_000_000 < len(data) == offsets[n] < 4_500_000
+    got = run_items(gpu, data, offsets, offsets[n])
+    wrong = [i for i in range(n) if got[i * D:(i + 1) * D] != digests[i]]
+    assert not wrong, f"{len(wrong)} of {n} digests differ, the first is item {wrong[0]} (GRID = {GRID})"
+    data_bytes = offsets[GRID + 3] + 77
+    assert offsets[n - 2] < data_bytes < offsets[n - 1] < offsets[n]
+    raw = data.tobytes()
+    clamped = digests[:GRID + 3] + [M.H(raw[offsets[GRID + 3]:data_bytes]), M.H(b"")]
+    assert clamped[-2:] != digests[-2:]
+    got = run_items(gpu, data, offsets, data_bytes)
+    wrong = [i for i in range(n) if got[i * D:(i + 1) * D] != clamped[i]]
+    assert not wrong, f"clamped: {len(wrong)} of {n} digests differ, the first is item {wrong[0]} (GRID = {GRID})"
 
 
 def test_rows_past_one_grid(gpu):
