@@ -591,6 +591,40 @@ int zk_merkle_build_dev(uint64_t n, void* d_tree, void* stream);      /* level 0
  * accepts every path.  An index >= n opens leaf n - 1.  One gather; k = 0 is ZK_OK and launches nothing, as is depth = 0. */
 int zk_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices /* k uint64 */, void* d_paths, void* stream);
 
+/* ---- Poseidon over Fr: permutation, fixed-length hash, sponge over rows and Merkle trees (csrc/poseidon.hip) -----------------
+ * Poseidon (Grassi et al., USENIX Security 2021) with S-box x^5 over Fr of either curve, state width t in {3, 4, 5}, R_F = 8 and
+ * R_P = 57 / 56 / 60 (circomlib's table, on both curves).  A round: add the round constants, S-box (every element in the first and
+ * last R_F / 2 rounds, element 0 in between), then state_i = sum_j M[i][j] state_j.  Round constants and M = 1 / (x_i + y_j) come
+ * from the paper's Grain LFSR; the library generates them on the host at first use and keeps one device
+ * table per (curve, t) until zk_shutdown.
+ *   perm_t             the permutation
+ *   hash(x_1..x_k)     perm_(k+1)([0, x_1, .., x_k])[0], k in {2, 3, 4}: circomlib's Poseidon(k)
+ *   sponge(row), L >= 1 elements: t = 3, the state starts as [L, 0, 0]; block i adds row[2i] to state[1] and row[2i+1], where it
+ *                      exists, to state[2]; perm_3 after every block; the digest is state[1]
+ *   tree               level 0 is n digests, parent = hash(left, right), a node without a right sibling is hashed with itself:
+ *                      the shape zk_merkle_layout describes, ZK_POSEIDON_NODE = 32 bytes per node (one canonical element)
+ * All inputs are canonical Fr elements (32 bytes) in device memory.  One permutation per lane, workgroups of 256 threads on a
+ * grid capped at 1024 workgroups: a pass takes a second item per thread first past 2^18 items.  ZK_ERR_ARG, before anything is
+ * launched or written, for n = 0 or n > 2^ZK_POSEIDON_MAX_LOG, a t, k or curve that does not exist, a null pointer, a vector that
+ * does not start at a multiple of 16 (indices: of 8) or an output that overlaps an input.  No entry point allocates beyond the
+ * parameter table; all of them only enqueue on `stream`. */
+#define ZK_POSEIDON_MAX_LOG 26
+#define ZK_POSEIDON_MAX_ROW (1u << 20)
+/* Host only (works without a GPU): *rf = R_F, *rp = R_P, out = the (R_F + R_P) t round constants in round order (constant
+ * [round][i] is added to state[i]) and then the t * t entries of M row-major, canonical 4-limb values.  Each output may be NULL. */
+int zk_poseidon_params(int curve, int t, int* rf, int* rp, uint64_t* out);
+/* state i (t elements at d_in + i t) -> perm_t of it at d_out + i t, i < n.  d_out == d_in is allowed, any other overlap is not. */
+int zk_poseidon_perm_dev(int curve, int t, uint64_t n, const void* d_in, void* d_out, void* stream);
+/* d_out[i] = hash(the k elements at d_rows + i k), i < n */
+int zk_poseidon_hash_dev(int curve, int k, uint64_t n, const void* d_rows, void* d_out, void* stream);
+/* d_digests[i] = sponge(the row_elems elements at d_rows + i row_elems), i < n; 1 <= row_elems <= ZK_POSEIDON_MAX_ROW */
+int zk_poseidon_sponge_rows_dev(int curve, uint64_t n, const void* d_rows, uint64_t row_elems, void* d_digests, void* stream);
+/* Levels 1 .. depth of d_tree (`nodes` nodes of 32 bytes) from level 0, which the caller has put at its front; n = 1 launches nothing. */
+int zk_poseidon_merkle_build_dev(int curve, uint64_t n, void* d_tree, void* stream);
+/* zk_merkle_paths_dev on 32-byte nodes: d_paths is k * depth nodes, entry (q, l) the sibling of the level-l ancestor of leaf
+ * d_indices[q] or that ancestor itself where it has no sibling; an index >= n opens leaf n - 1; k = 0 and depth = 0 launch nothing. */
+int zk_poseidon_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices /* k uint64 */, void* d_paths, void* stream);
+
 /* ---- FRI polynomial commitment: low-degree extension, fold and row gather (csrc/fri.hip) ------------------------------------
  * The device side of commitment/polynomial/fri.py (the reference has no FRI).  A layer f of M = 2h canonical Fr elements on a
  * coset s <w> (w of order M) is stored in PAIR ORDER: g[2j] = f[j], g[2j+1] = f[j+h] for j < h, the values at x_j = s w^j and at

@@ -44,6 +44,8 @@ MLPCS_MAX_LOG = 24  # ZK_MLPCS_MAX_LOG: a multilinear KZG commitment has at most
 MLE_TILE_LOG = 8  # ZK_MLE_TILE_LOG: variables one launch of the multilinear kernels folds per 256-element tile
 MERKLE_DIGEST = 64  # ZK_MERKLE_DIGEST: bytes per BLAKE2b-512 digest, and per node of a Merkle tree
 MERKLE_MAX_LOG = 26  # ZK_MERKLE_MAX_LOG: a Merkle tree has at most 2^26 leaves
+POSEIDON_MAX_LOG = 26  # ZK_POSEIDON_MAX_LOG: a Poseidon call takes at most 2^26 states, rows or leaves
+POSEIDON_MAX_ROW = 1 << 20  # ZK_POSEIDON_MAX_ROW: elements per row of the Poseidon sponge
 FRI_MAX_LOG = 26  # ZK_FRI_MAX_LOG: a FRI layer has at most 2^26 elements
 GKR_MAX_LOG = 24  # ZK_GKR_MAX_LOG: a layer of a GKR circuit has at most 2^24 wires
 GKR_LONG_ROW = 64  # ZK_GKR_LONG_ROW: CSR rows with more entries leave the lane-per-row kernel of the GKR passes
@@ -156,6 +158,12 @@ SIGNATURES = {
     "zk_merkle_layout": (_i, [_u64, ctypes.POINTER(_i), _u64p, _u64p]),
     "zk_merkle_build_dev": (_i, [_u64, _vp, _vp]),
     "zk_merkle_paths_dev": (_i, [_u64, _vp, _u64, _vp, _vp, _vp]),
+    "zk_poseidon_params": (_i, [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), _u64p]),
+    "zk_poseidon_perm_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp]),
+    "zk_poseidon_hash_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp]),
+    "zk_poseidon_sponge_rows_dev": (_i, [_i, _u64, _vp, _u64, _vp, _vp]),
+    "zk_poseidon_merkle_build_dev": (_i, [_i, _u64, _vp, _vp]),
+    "zk_poseidon_merkle_paths_dev": (_i, [_u64, _vp, _u64, _vp, _vp, _vp]),
     "zk_fri_lde_dev": (_i, [_i, _i, _i, _u64, _vp, _u64p, _vp, _vp, _vp]),
     "zk_fri_fold_dev": (_i, [_i, _i, _vp, _u64p, _u64p, _vp, _vp]),
     "zk_fri_rows_dev": (_i, [_u64, _u64, _vp, _u64, _vp, _vp, _vp]),

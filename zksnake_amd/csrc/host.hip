@@ -18,6 +18,7 @@
 
 extern "C" void zk_ntt_free_cache(void);
 extern "C" void zk_msm_free_all(void);
+extern "C" void zk_poseidon_free_cache(void);
 extern "C" void zk_ntt_stream_released(void* stream);
 
 namespace zkmi {
@@ -435,6 +436,7 @@ int zk_debug_spin_dev(void* stream, uint64_t microseconds) {
 int zk_shutdown(void) {
     zk_msm_free_all();
     zk_ntt_free_cache();
+    zk_poseidon_free_cache();
     dev_cache_release();
     return ZK_OK;
 }
