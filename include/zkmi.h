@@ -621,8 +621,7 @@ int zk_poseidon_hash_dev(int curve, int k, uint64_t n, const void* d_rows, void*
 int zk_poseidon_sponge_rows_dev(int curve, uint64_t n, const void* d_rows, uint64_t row_elems, void* d_digests, void* stream);
 /* Levels 1 .. depth of d_tree (`nodes` nodes of 32 bytes) from level 0, which the caller has put at its front; n = 1 launches nothing. */
 int zk_poseidon_merkle_build_dev(int curve, uint64_t n, void* d_tree, void* stream);
-/* zk_merkle_paths_dev on 32-byte nodes: d_paths is k * depth nodes, entry (q, l) the sibling of the level-l ancestor of leaf
- * d_indices[q] or that ancestor itself where it has no sibling; an index >= n opens leaf n - 1; k = 0 and depth = 0 launch nothing. */
+/* zk_merkle_paths_dev on 32-byte nodes, the same gather and the same rules: d_paths is k * depth nodes. */
 int zk_poseidon_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices /* k uint64 */, void* d_paths, void* stream);
 
 /* ---- FRI polynomial commitment: low-degree extension, fold and row gather (csrc/fri.hip) ------------------------------------

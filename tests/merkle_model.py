@@ -5,6 +5,8 @@ everything that is compared with this model is compared with == on bytes."""
 
 import hashlib
 
+import tree_model as T
+
 DIGEST = 64
 MAX_LOG = 26
 
@@ -19,11 +21,7 @@ def leaf_digests(items):
 
 def levels(leaves):
     """[level 0, level 1, .., [root]] from the leaf digests"""
-    out = [list(leaves)]
-    while len(out[-1]) > 1:
-        cur = out[-1]
-        out.append([H(cur[i] + (cur[i + 1] if i + 1 < len(cur) else cur[i])) for i in range(0, len(cur), 2)])
-    return out
+    return T.levels(leaves, lambda left, right: H(left + right))
 
 
 def layout(n):
@@ -48,12 +46,7 @@ def root(lv):
 
 def path(lv, index):
     """depth entries: the sibling at every level below the root, the node itself where there is none"""
-    out = []
-    for level in lv[:-1]:
-        sib = index ^ 1
-        out.append(level[sib] if sib < len(level) else level[index])
-        index >>= 1
-    return out
+    return T.path(lv, index)
 
 
 def verify(commitment, proof, index, element):

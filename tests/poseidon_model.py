@@ -6,6 +6,8 @@ implementations that have to agree by ==.  Nothing here imports the library.
 
 import functools
 
+import tree_model as T
+
 R = {
     "BN254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
     "BLS12_381": 52435875175126190479447740508185965837690552500527637822603658699938581184513,
@@ -108,21 +110,12 @@ def sponge(curve, row):
 
 def levels(curve, leaves):
     """every level of the tree over the leaf digests, level 0 first; a node without a right sibling is hashed with itself"""
-    lv = [list(leaves)]
-    while len(lv[-1]) > 1:
-        cur = lv[-1]
-        lv.append([hash(curve, [cur[i], cur[min(i + 1, len(cur) - 1)]]) for i in range(0, len(cur), 2)])
-    return lv
+    return T.levels(leaves, lambda left, right: hash(curve, [left, right]))
 
 
 def path(lv, index):
     """the siblings of leaf `index`, leaf level first; the node itself where it has no sibling"""
-    out = []
-    for level in lv[:-1]:
-        sib = index ^ 1
-        out.append(level[sib if sib < len(level) else index])
-        index >>= 1
-    return out
+    return T.path(lv, index)
 
 
 def root(lv):

@@ -235,6 +235,16 @@ def test_paths_at_every_index(gpu, n):
     assert run_paths(gpu, n, tree.ptr, indices) == want_paths(lv, indices)
 
 
+@pytest.mark.parametrize("n", [5, 9])
+def test_paths_of_indices_past_the_leaves(gpu, n):
+    """an index at or past n opens the last leaf: the clamp of the kernel, which the Python layer never reaches"""
+    leaves = rand_bytes(n * D, 300 + n).tobytes()
+    lv = M.levels(chunks(leaves, D))
+    tree = run_build(gpu, n, leaves)
+    indices = list(range(n)) + [n, n + 7, 2**63]
+    assert run_paths(gpu, n, tree.ptr, indices) == want_paths(lv, [min(i, n - 1) for i in indices])
+
+
 def test_paths_in_a_large_tree(gpu, big):
     _, lv, tree = big
     n = N_BIG

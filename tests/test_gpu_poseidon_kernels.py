@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import poseidon_model as M
+import tree_model as T
 from zksnake_amd import _native as N
 from zksnake_amd.device import DeviceBuffer
 
@@ -172,12 +173,7 @@ def test_sponge_takes_a_second_item(gpu, curve):
 
 def model_levels(curve, leaves):
     """M.levels with every distinct (left, right) of the tree hashed once"""
-    pair = functools.lru_cache(maxsize=None)(lambda left, right: M.hash(curve, [left, right]))
-    lv = [list(leaves)]
-    while len(lv[-1]) > 1:
-        cur = lv[-1]
-        lv.append([pair(cur[i], cur[min(i + 1, len(cur) - 1)]) for i in range(0, len(cur), 2)])
-    return lv
+    return T.levels(leaves, functools.lru_cache(maxsize=None)(lambda left, right: M.hash(curve, [left, right])))
 
 
 def build(gpu, curve, leaves):
@@ -239,6 +235,49 @@ def test_merkle_paths(gpu, curve, n):
     untouched = Out(gpu, depth)
     N.check(gpu.zk_poseidon_merkle_paths_dev(n, tree.ptr, 0, d_idx.ptr, untouched.ptr, None))
     assert (untouched.limbs().view(np.uint8) == POISON).all()
+
+
+def numbered_tree(n):
+    """(levels of node numbers, the tree as (nodes, 4) limbs): limb c of node j holds 4 j + c, so every word of the tree is its
+    own value and a gathered node names where it came from"""
+    lv, width = [], n
+    while True:
+        first = lv[-1][-1] + 1 if lv else 0
+        lv.append(list(range(first, first + width)))
+        if width == 1:
+            break
+        width = (width + 1) // 2
+    nodes = lv[-1][0] + 1
+    return lv, np.arange(4 * nodes, dtype=np.uint64).reshape(nodes, 4)
+
+
+def run_numbered_paths(gpu, n, indices):
+    """(k, depth, 4) limbs gathered from the numbered tree, and the same from the model's paths"""
+    lv, nodes = numbered_tree(n)
+    depth, k = len(lv) - 1, len(indices)
+    tree = DeviceBuffer.from_numpy(nodes)
+    d_idx = DeviceBuffer.from_numpy(np.array(indices, dtype=np.uint64))
+    out = Out(gpu, k * depth)
+    N.check(gpu.zk_poseidon_merkle_paths_dev(n, tree.ptr, k, d_idx.ptr, out.ptr, None))
+    table = np.array([T.path(lv, i) for i in range(n)], dtype=np.int64).reshape(n, depth)
+    return out.limbs().reshape(k, depth, 4), nodes[table[np.array(indices, dtype=np.int64)]]
+
+
+@pytest.mark.parametrize("n", (1, 2, 3, 5, 8, 13, 257))
+def test_merkle_paths_at_every_index(gpu, n):
+    """the gather alone, on a tree that was uploaded and not hashed: every index and some again, depth 0 to 9, odd widths at the
+    bottom, in the middle and below the root, past one workgroup"""
+    got, want = run_numbered_paths(gpu, n, list(range(n)) + [0, n - 1, n - 1, n // 2])
+    assert got.shape == want.shape and (got == want).all()
+
+
+def test_merkle_paths_past_one_grid(gpu):
+    n, k = 13, (1 << 16) + 1   # k * depth = 2^18 + 4 entries: threads 0 .. 3 take a second one
+    rnd = random.Random(21)
+    indices = [rnd.randrange(n) for _ in range(k)]
+    indices[0], indices[-1] = n - 1, n - 1
+    got, want = run_numbered_paths(gpu, n, indices)
+    assert got.shape == want.shape == (k, 4, 4) and k * 4 > GRID and (got == want).all()
 
 
 def test_one_leaf_has_empty_paths(gpu):

@@ -4,8 +4,9 @@
 so a kernel that moved to another translation unit is compared with itself.  Compared per function: the `llvm-objdump -d` text
 without addresses and comments, and for kernels (symbols with a `.kd` descriptor) the register, LDS and scratch figures of the
 metadata notes.  Two things that belong to a code object's layout and not to the code are masked: the 32-bit literals of the
-`s_add_u32` / `s_addc_u32` pair after an `s_getpc_b64` (the distance to a constant table or a callee), and objdump's `...`
-marker of a zero-filled gap behind a function.  usage: isa_diff.py <dirA> <dirB>; exit status 1 unless everything is equal."""
+`s_add_u32` / `s_addc_u32` pair after an `s_getpc_b64` (the distance to a constant table or a callee), and what fills the gap
+behind a function: objdump's `...` marker of zeros, and the run of `s_nop 0` that pads the end of a text section and is listed
+with whichever function happens to come last in it.  usage: isa_diff.py <dirA> <dirB>; exit status 1 unless everything is equal."""
 import glob
 import os
 import re
@@ -31,6 +32,8 @@ def normalise(lines):
             pc.discard(m.group(2))
             line = f"{m.group(1)} {m.group(2)}, {m.group(3)}, <pc-relative>"
         out.append(line)
+    while out and out[-1] == "s_nop 0":   # no function ends in one: it returns, branches or ends the program
+        out.pop()
     return out
 
 

@@ -5,14 +5,16 @@ same machine: a hashlib commit and one hashlib open at 2^16 and 2^20.  Every tim
 synchronisation or a download, and is repeated; the report has the median and the spread (min, max).
 
     python tools/merkle_bench.py [--logs 16 20 24] [--host-log 20] [--baseline-logs 16 20] [--repeats 7] [--out FILE]
-                                 [--variant-lib OTHER_LIBZKMI --variant-logs 12 16 20]
+                                 [--variant-lib OTHER_LIBZKMI --variant-logs 12 16 20 --variant-path-logs 16 20]
 
 The build is also timed from every level upwards (the tree above level l is itself a tree over that level's nodes, in place), which
 lists what each launch costs; "launches" names them by the rule of csrc/merkle.hip, one launch per level.
 
 --variant-lib: another build of the library (an experiment on csrc/merkle.hip) whose zk_merkle_build_dev is timed against this
 one's on the same device memory, alternated run by run, at least six runs each.  This is how the one-workgroup tail kernel was
-decided (EXPERIMENTS.md "Merkle trees"): the variant finished every level of at most 1024 nodes in one workgroup."""
+decided (EXPERIMENTS.md "Merkle trees"): the variant finished every level of at most 1024 nodes in one workgroup.  The two path
+gathers, zk_merkle_paths_dev and zk_poseidon_merkle_paths_dev at 2^10 indices, are alternated in the same way; they only copy, so
+the tree they read is random bytes and the two libraries' outputs are compared with ==."""
 
 import argparse
 import ctypes
@@ -29,7 +31,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from zksnake_amd import _native as N  # noqa: E402
 from zksnake_amd.commitment.vector import Merkle  # noqa: E402
-from zksnake_amd.commitment.vector.merkle import _host_leaves, _layout  # noqa: E402
+from zksnake_amd.commitment.vector._tree import _layout  # noqa: E402
+from zksnake_amd.commitment.vector.merkle import _host_leaves  # noqa: E402
 from zksnake_amd.device import DeviceBuffer  # noqa: E402
 from zksnake_amd.frvec import DevVec  # noqa: E402
 
@@ -151,35 +154,64 @@ def bench_baseline(log_n, repeats, items=None):
             "device_open_from_host_list": timed(lambda: scheme.open(items, 7), repeats)}
 
 
-def bench_variant(lib, path, logs, repeats):
-    """zk_merkle_build_dev of this library and of the one at `path`, alternated, on one tree"""
+def variant_lib(path):
     other = ctypes.CDLL(path)
-    other.zk_merkle_build_dev.restype, other.zk_merkle_build_dev.argtypes = N.SIGNATURES["zk_merkle_build_dev"]
-    other.zk_init.restype, other.zk_init.argtypes = N.SIGNATURES["zk_init"]
+    for name in ("zk_init", "zk_merkle_build_dev", "zk_merkle_paths_dev", "zk_poseidon_merkle_paths_dev"):
+        getattr(other, name).restype, getattr(other, name).argtypes = N.SIGNATURES[name]
     if other.zk_init(0) != N.ZK_OK:
         sys.exit("the variant library does not initialise")
+    return other
+
+
+def alternate(lib, other, call, result, repeats):
+    """call(l) on this library and on the variant, run by run, each run ended by a device synchronisation; two warm-up rounds.
+    result() is what the last call left behind, and must be the same for both"""
+    ms, left = {"this": [], "variant": []}, {}
+    for rep in range(repeats + 2):
+        for name, l in (("this", lib), ("variant", other)):
+            t0 = time.perf_counter()
+            if call(l) != N.ZK_OK:
+                sys.exit(f"{name}: the call failed")
+            N.check(lib.zk_dev_synchronize())
+            if rep >= 2:
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+            left[name] = result()
+    assert left["this"] == left["variant"], "the two libraries give different results"
+    a, b = stats(ms["this"]), stats(ms["variant"])
+    return {"this": a, "variant": b, "gain_of_this_ms": round(b["median_ms"] - a["median_ms"], 4),
+            "spread_of_variant_ms": round(b["max_ms"] - b["min_ms"], 4), "this_inside_variant_spread_or_below": a["median_ms"] <= b["max_ms"]}
+
+
+def bench_variant(lib, other, logs, repeats):
+    """zk_merkle_build_dev of this library and of the variant, alternated, on one tree"""
     rows = []
     for log_n in logs:
         n = 1 << log_n
         nodes = _layout(n)[2]
         tree = DeviceBuffer(nodes * D)
         tree.upload(np.random.default_rng(log_n).integers(0, 256, size=n * D, dtype=np.uint8))
-        ms = {"this": [], "variant": []}
-        roots = {}
-        for rep in range(repeats + 2):
-            for name, l in (("this", lib), ("variant", other)):
-                t0 = time.perf_counter()
-                if l.zk_merkle_build_dev(n, tree.ptr, None) != N.ZK_OK:
-                    sys.exit(f"{name}: build failed")
-                N.check(lib.zk_dev_synchronize())
-                if rep >= 2:   # two warm-up rounds
-                    ms[name].append((time.perf_counter() - t0) * 1e3)
-                roots[name] = tree.download((D,), np.uint8, (nodes - 1) * D).tobytes()
-        assert roots["this"] == roots["variant"], "the two builds give different roots"
-        a, b = stats(ms["this"]), stats(ms["variant"])
-        rows.append({"log_n": log_n, "this": a, "variant": b, "gain_of_this_ms": round(b["median_ms"] - a["median_ms"], 4),
-                     "spread_of_variant_ms": round(b["max_ms"] - b["min_ms"], 4)})
+        rows.append({"log_n": log_n, **alternate(lib, other, lambda l: l.zk_merkle_build_dev(n, tree.ptr, None),
+                                                 lambda: tree.download((D,), np.uint8, (nodes - 1) * D).tobytes(), repeats)})
         tree.free()
+    return rows
+
+
+def bench_variant_paths(lib, other, logs, repeats, k=1 << 10):
+    """the two gathers of this library and of the variant, alternated, k indices into one tree of each node size"""
+    rows = []
+    for log_n in logs:
+        n = 1 << log_n
+        depth, _, nodes = _layout(n)
+        d_idx = DeviceBuffer.from_numpy(np.random.default_rng(log_n).integers(0, n, size=k, dtype=np.uint64))
+        for entry, node in (("zk_merkle_paths_dev", 64), ("zk_poseidon_merkle_paths_dev", 32)):
+            tree = DeviceBuffer.from_numpy(np.random.default_rng(node + log_n).integers(0, 256, size=nodes * node, dtype=np.uint8))
+            paths = DeviceBuffer(k * depth * node)
+            rows.append({"entry": entry, "log_n": log_n, "indices": k,
+                         **alternate(lib, other, lambda l: getattr(l, entry)(n, tree.ptr, k, d_idx.ptr, paths.ptr, None),
+                                     lambda: paths.download((k * depth * node,), np.uint8).tobytes(), repeats)})
+            tree.free()
+            paths.free()
+        d_idx.free()
     return rows
 
 
@@ -191,6 +223,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--variant-lib")
     ap.add_argument("--variant-logs", type=int, nargs="*", default=[12, 16, 20])
+    ap.add_argument("--variant-path-logs", type=int, nargs="*", default=[16, 20])
     ap.add_argument("--out")
     args = ap.parse_args()
     lib = N.ensure_gpu()
@@ -201,7 +234,9 @@ def main():
         return row
 
     if args.variant_lib:
-        report["build_this_against_variant"] = emit("build_this_against_variant", bench_variant(lib, args.variant_lib, args.variant_logs, max(args.repeats, 6)))
+        other = variant_lib(args.variant_lib)
+        report["build_this_against_variant"] = emit("build_this_against_variant", bench_variant(lib, other, args.variant_logs, max(args.repeats, 6)))
+        report["paths_this_against_variant"] = emit("paths_this_against_variant", bench_variant_paths(lib, other, args.variant_path_logs, max(args.repeats, 6)))
     for log_n in args.logs:
         report["resident"].append(emit("resident", bench_resident(lib, log_n, args.repeats)))
     items = None

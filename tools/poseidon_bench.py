@@ -26,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from zksnake_amd import _native as N  # noqa: E402
-from zksnake_amd.commitment.vector.merkle import _layout  # noqa: E402
+from zksnake_amd.commitment.vector._tree import _layout  # noqa: E402
 from zksnake_amd.device import DeviceBuffer  # noqa: E402
 from zksnake_amd.hash import Poseidon  # noqa: E402
 

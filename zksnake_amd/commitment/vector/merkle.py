@@ -3,7 +3,7 @@
 Leaf digests, every level of the tree and the opening paths come from csrc/merkle.hip (one digest per lane); `verify` is log n
 hashes and stays on the host with hashlib, the reference's own loop.  `Merkle.tree(vector)` keeps the tree in device memory, so
 that many indices are opened from one build (`MerkleTree.open_many`: one launch, one download); `commit` and `open` are thin
-wrappers over it.
+wrappers over it.  What does not depend on the hash -- the layout, the resident tree, those wrappers -- is `_tree.py`.
 
 A `vector` is one of
   * a sequence of bytes-like items of any lengths (the reference's shape): joined on the host, uploaded once;
@@ -20,45 +20,27 @@ Differences from the reference:
      range(n) raises IndexError instead of being opened as some other leaf.
 """
 
-import ctypes
 import hashlib
-import operator
 
 import numpy as np
 
 from ... import _native as N
 from ...device import DeviceBuffer
 from ...frvec import DevVec
-from .base import VectorCommitmentScheme
+from ._tree import MAX_LEAVES, DeviceTree, TreeScheme, _layout, _leaf_count  # noqa: F401 - MAX_LEAVES is part of this module
 
 DIGEST = N.MERKLE_DIGEST
-MAX_LEAVES = 1 << N.MERKLE_MAX_LOG
 
 
-def _layout(n):
-    """(depth, first node of every level, nodes) of a tree over n leaves: host arithmetic of the library, no GPU"""
-    depth, nodes = ctypes.c_int(0), ctypes.c_uint64(0)
-    offsets = np.zeros(N.MERKLE_MAX_LOG + 1, dtype=np.uint64)
-    N.check(N.load().zk_merkle_layout(n, ctypes.byref(depth), N.u64p(offsets), ctypes.byref(nodes)))
-    return depth.value, [int(x) for x in offsets[:depth.value + 1]], nodes.value
+class MerkleTree(DeviceTree):
+    """a tree of 64-byte nodes: `open_many` gives (k, depth, 64) uint8 and `level` (n_l, 64) uint8, the root and the entries of a
+    proof are bytes"""
 
+    KIND, DTYPE, WIDTH, PATHS = "Merkle", np.uint8, DIGEST, "zk_merkle_paths_dev"
 
-def _leaf_count(n):
-    if n == 0:
-        raise IndexError("a Merkle tree needs at least one leaf")
-    if n > MAX_LEAVES:
-        raise ValueError(f"a Merkle tree has at most 2^{N.MERKLE_MAX_LOG} leaves")
-    return n
-
-
-class MerkleTree:
-    """a tree over n leaves, resident in device memory (level 0 first, 64 bytes per node) until release()"""
-
-    def __init__(self, n, buf):
-        self.n = _leaf_count(n)
-        self.depth, self._offsets, self.nodes = _layout(n)
-        self._buf = buf   # the tree's one owner
-        self.root = None if buf is None else buf.download((DIGEST,), np.uint8, (self.nodes - 1) * DIGEST).tobytes()
+    @staticmethod
+    def _values(nodes):
+        return [row.tobytes() for row in nodes]
 
     @classmethod
     def from_device_rows(cls, n, ptr, row_bytes):
@@ -76,48 +58,6 @@ class MerkleTree:
         except BaseException:
             tree.free()
             raise
-
-    def _device(self):
-        if self._buf is None or self._buf.ptr is None:
-            raise RuntimeError("the tree has been released")
-        return self._buf
-
-    def _indices(self, indices):
-        idx = [operator.index(i) for i in indices]
-        for i in idx:
-            if not 0 <= i < self.n:
-                raise IndexError(f"index {i} is outside a vector of {self.n} elements")
-        return np.array(idx, dtype=np.uint64)
-
-    def open_many(self, indices):
-        """(k, depth, 64) uint8: row q is the proof of indices[q], leaf level first"""
-        idx = self._indices(indices)
-        tree, k = self._device(), idx.shape[0]
-        if k == 0 or self.depth == 0:
-            return np.zeros((k, self.depth, DIGEST), dtype=np.uint8)
-        d_idx = DeviceBuffer.from_numpy(idx)
-        d_paths = DeviceBuffer(k * self.depth * DIGEST)
-        try:
-            N.check(N.load().zk_merkle_paths_dev(self.n, tree.ptr, k, d_idx.ptr, d_paths.ptr, None))
-            return d_paths.download((k, self.depth, DIGEST), np.uint8)
-        finally:
-            d_idx.free()
-            d_paths.free()
-
-    def open(self, index):
-        return [row.tobytes() for row in self.open_many([index])[0]]
-
-    def level(self, l):
-        """the nodes of level l (0: the leaf digests, depth: the root) as (n_l, 64) uint8"""
-        if not 0 <= l <= self.depth:
-            raise IndexError(f"level {l} of a tree of depth {self.depth}")
-        end = self._offsets[l + 1] if l < self.depth else self.nodes
-        return self._device().download((end - self._offsets[l], DIGEST), np.uint8, self._offsets[l] * DIGEST)
-
-    def release(self):
-        if self._buf is not None:
-            self._buf.free()
-            self._buf = None
 
 
 def _host_leaves(vector):
@@ -144,16 +84,13 @@ def _host_leaves(vector):
     return n, data, None, offsets
 
 
-class Merkle(VectorCommitmentScheme):
+class Merkle(TreeScheme):
 
     def __init__(self, alg="blake2b"):
         super().__init__()
         if alg != "blake2b":
             raise ValueError(f"only alg='blake2b' has a kernel (there is no CPU fallback), not {alg!r}")
         self.alg = alg
-
-    def setup(self):
-        pass
 
     def _hash(self, data):
         return hashlib.blake2b(data).digest()
@@ -190,20 +127,6 @@ class Merkle(VectorCommitmentScheme):
             for buf in owned:
                 if buf is not None:
                     buf.free()
-
-    def commit(self, vector):
-        tree = self.tree(vector)
-        try:
-            return tree.root
-        finally:
-            tree.release()
-
-    def open(self, vector, index):
-        tree = self.tree(vector)
-        try:
-            return tree.open(index)
-        finally:
-            tree.release()
 
     def verify(self, commitment, proof, index, element):
         digest = self._hash(element)

@@ -3,7 +3,7 @@
 A leaf is a row of L >= 1 field elements and its digest is `Poseidon.sponge(row)` (the length sits in the capacity element, so a
 leaf digest is never a node); a node is `Poseidon.hash(left, right)`, circomlib's Poseidon(2).  The shape is `Merkle`'s: a node
 without a right sibling is hashed with itself, depth = ceil(log2 n), one leaf is its own root, and a proof has `depth` entries,
-the node itself where it has no sibling.  Nodes are canonical Fr elements, 32 bytes.  Leaf digests, every level and the opening
+the node itself where it has no sibling (`_tree.py` holds all of that).  Nodes are canonical Fr elements, 32 bytes.  Leaf digests, every level and the opening
 paths come from csrc/poseidon.hip (one permutation per lane); `verify` is 1 + ceil(L / 2) + depth permutations in Python integers
 and needs no GPU.
 
@@ -24,75 +24,23 @@ from ... import _native as N
 from ...device import DeviceBuffer
 from ...frvec import DevVec
 from ...hash import Poseidon
-from .base import VectorCommitmentScheme
-from .merkle import _layout
+from ._tree import MAX_LEAVES, DeviceTree, TreeScheme, _layout, _leaf_count  # noqa: F401 - MAX_LEAVES is part of this module
 
 NODE = 32
-MAX_LEAVES = 1 << N.POSEIDON_MAX_LOG
 
 
-def _leaf_count(n):
-    if n == 0:
-        raise IndexError("a Merkle tree needs at least one leaf")
-    if n > MAX_LEAVES:
-        raise ValueError(f"a Poseidon Merkle tree has at most 2^{N.POSEIDON_MAX_LOG} leaves")
-    return n
+class PoseidonMerkleTree(DeviceTree):
+    """a tree of 32-byte nodes: `open_many` gives (k, depth, 4) uint64 limbs and `level` (n_l, 4) limbs, the root and the entries
+    of a proof are ints"""
+
+    KIND, DTYPE, WIDTH, PATHS = "Poseidon Merkle", np.uint64, 4, "zk_poseidon_merkle_paths_dev"
+
+    @staticmethod
+    def _values(nodes):
+        return N.limbs_to_ints(nodes) if len(nodes) else []
 
 
-class PoseidonMerkleTree:
-    """a tree over n leaves, resident in device memory (level 0 first, 32 bytes per node) until release()"""
-
-    def __init__(self, n, buf):
-        self.n = _leaf_count(n)
-        self.depth, self._offsets, self.nodes = _layout(n)
-        self._buf = buf   # the tree's one owner
-        self.root = None if buf is None else N.limbs_to_ints(buf.download((1, 4), np.uint64, (self.nodes - 1) * NODE))[0]
-
-    def _device(self):
-        if self._buf is None or self._buf.ptr is None:
-            raise RuntimeError("the tree has been released")
-        return self._buf
-
-    def _indices(self, indices):
-        idx = [operator.index(i) for i in indices]
-        for i in idx:
-            if not 0 <= i < self.n:
-                raise IndexError(f"index {i} is outside a vector of {self.n} elements")
-        return np.array(idx, dtype=np.uint64)
-
-    def open_many(self, indices):
-        """(k, depth, 4) uint64: row q is the proof of indices[q] as limbs, leaf level first"""
-        idx = self._indices(indices)
-        tree, k = self._device(), idx.shape[0]
-        if k == 0 or self.depth == 0:
-            return np.zeros((k, self.depth, 4), dtype=np.uint64)
-        d_idx = DeviceBuffer.from_numpy(idx)
-        d_paths = DeviceBuffer(k * self.depth * NODE)
-        try:
-            N.check(N.load().zk_poseidon_merkle_paths_dev(self.n, tree.ptr, k, d_idx.ptr, d_paths.ptr, None))
-            return d_paths.download((k, self.depth, 4), np.uint64)
-        finally:
-            d_idx.free()
-            d_paths.free()
-
-    def open(self, index):
-        path = self.open_many([index])[0]
-        return N.limbs_to_ints(path) if len(path) else []
-
-    def level(self, l):
-        """the nodes of level l (0: the leaf digests, depth: the root) as (n_l, 4) uint64 limbs"""
-        if not 0 <= l <= self.depth:
-            raise IndexError(f"level {l} of a tree of depth {self.depth}")
-        end = self._offsets[l + 1] if l < self.depth else self.nodes
-        return self._device().download((end - self._offsets[l], 4), np.uint64, self._offsets[l] * NODE)
-
-    def release(self):
-        if self._buf is not None:
-            self._buf.free()
-            self._buf = None
-
-
-class PoseidonMerkle(VectorCommitmentScheme):
+class PoseidonMerkle(TreeScheme):
 
     def __init__(self, curve="BN254"):
         super().__init__()
@@ -100,20 +48,17 @@ class PoseidonMerkle(VectorCommitmentScheme):
         self.curve = curve
         self.order = self.hasher.p
 
-    def setup(self):
-        pass
-
     def _leaves(self, vector):
         """(n, L, source) of a vector, checked on the host; no device call"""
         if isinstance(vector, DevVec):
-            _leaf_count(vector.n)
+            _leaf_count(vector.n, PoseidonMerkleTree.KIND)
             return self.hasher.rows_in(vector, 1, range(1, 2), "PoseidonMerkle")
         if isinstance(vector, np.ndarray):
             if vector.ndim == 3:
-                _leaf_count(vector.shape[0])
+                _leaf_count(vector.shape[0], PoseidonMerkleTree.KIND)
             return self.hasher.rows_in(vector, None, range(1, N.POSEIDON_MAX_ROW + 1), "PoseidonMerkle")
         items = vector if isinstance(vector, (list, tuple)) else list(vector)
-        _leaf_count(len(items))
+        _leaf_count(len(items), PoseidonMerkleTree.KIND)
         flat = [isinstance(item, (int, np.integer)) for item in items]
         if all(flat):
             items = [[item] for item in items]
@@ -137,23 +82,12 @@ class PoseidonMerkle(VectorCommitmentScheme):
             tree.free()
             raise
 
-    def commit(self, vector):
-        tree = self.tree(vector)
-        try:
-            return tree.root
-        finally:
-            tree.release()
-
     def open(self, vector, index):
         leaves = self._leaves(vector)
         index = operator.index(index)
         if not 0 <= index < leaves[0]:
             raise IndexError(f"index {index} is outside a vector of {leaves[0]} elements")
-        tree = self._build(*leaves)
-        try:
-            return tree.open(index)
-        finally:
-            tree.release()
+        return self._use(self._build(*leaves), lambda tree: tree.open(index))
 
     def verify(self, commitment, proof, index, element):
         """on the host: element is the leaf, an int or a row of ints"""

@@ -128,6 +128,7 @@ inline int log2_u64(uint64_t n) {
 }
 
 // ---- argument checks: byte spans of the caller's buffers ------------------------------------------------------
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }   // what a 16-byte vector access needs
 inline bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + b_bytes && y < x + a_bytes;

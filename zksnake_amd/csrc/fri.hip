@@ -73,8 +73,6 @@ __global__ __launch_bounds__(MLE_TILE) void fri_rows_kernel(uint64_t n_rows, uin
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-static bool fri_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // 1 / 2 = (r + 1) / 2 as limbs: (r - 1) / 2 + 1
 template <class P>
 static Fp<P> fri_half_mont() {
@@ -95,7 +93,7 @@ static int fri_lde_impl(int curve, int log_n, int log_blowup, uint64_t n_coeffs,
         return fail(ZK_ERR_ARG, "fri_lde: need log_n >= 0, log_blowup >= 1 and log_n + log_blowup <= 26");
     if (n_coeffs > (1ull << log_n)) return fail(ZK_ERR_ARG, "fri_lde: more than 2^log_n coefficients");
     if (!shift || !d_work || !d_out || (!d_coeffs && n_coeffs)) return fail(ZK_ERR_ARG, "fri_lde: null pointer");
-    if (!fri_aligned16(d_coeffs) || !fri_aligned16(d_work) || !fri_aligned16(d_out))
+    if (!aligned16(d_coeffs) || !aligned16(d_work) || !aligned16(d_out))
         return fail(ZK_ERR_ARG, "fri_lde: vectors start at a multiple of 16");
     const int log_size = log_n + log_blowup;
     const uint64_t eb = P::W * 4, size = 1ull << log_size, h = size >> 1;
@@ -116,7 +114,7 @@ template <class P>
 static int fri_fold_impl(int log_m, const void* d_in, const uint64_t* c, const uint64_t* w_inv, void* d_out, hipStream_t st) {
     if (log_m < 1 || log_m > FRI_MAX_LOG) return fail(ZK_ERR_ARG, "fri_fold: need 1 <= log_m <= 26");
     if (!d_in || !d_out || !c || !w_inv) return fail(ZK_ERR_ARG, "fri_fold: null pointer");
-    if (!fri_aligned16(d_in) || !fri_aligned16(d_out)) return fail(ZK_ERR_ARG, "fri_fold: layers start at a multiple of 16");
+    if (!aligned16(d_in) || !aligned16(d_out)) return fail(ZK_ERR_ARG, "fri_fold: layers start at a multiple of 16");
     const uint64_t eb = P::W * 4, h = 1ull << (log_m - 1);
     const void* in[1] = {d_in};
     const uint64_t len[1] = {2 * h * eb};
@@ -135,7 +133,7 @@ static int fri_rows(uint64_t n_rows, uint64_t row_bytes, const void* d_rows, uin
     if (!d_rows) return fail(ZK_ERR_ARG, "fri_rows: null rows");
     if (k == 0) return ZK_OK;
     if (!d_indices || !d_out) return fail(ZK_ERR_ARG, "fri_rows: null pointer");
-    if (!fri_aligned16(d_rows) || !fri_aligned16(d_out) || ((uintptr_t)d_indices & 7))
+    if (!aligned16(d_rows) || !aligned16(d_out) || ((uintptr_t)d_indices & 7))
         return fail(ZK_ERR_ARG, "fri_rows: rows and output start at a multiple of 16, the indices at a multiple of 8");
     const void* in[2] = {d_rows, d_indices};
     const uint64_t len[2] = {n_rows * row_bytes, k * 8};

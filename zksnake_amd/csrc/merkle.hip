@@ -7,15 +7,13 @@
 // by 32 is a swap of halves and costs nothing.  BLAKE2b as hashlib.new("blake2b", data) computes it: RFC 7693, 64-byte digest, no
 // key, salt or personalisation, so h[0] starts as IV[0] ^ 0x01010040.
 //
-// A tree is its levels one after the other, 64 bytes per node: level 0 (the n leaf digests) first, level l has
-// ceil(n_(l-1) / 2) nodes, the root is the last node.  A node without a right sibling is hashed with itself (the reference's
-// _build_tree).  Workgroups of MLE_TILE threads on the capped strided grid of fr_sum.hip.h; plain C++, no atomics.
-#include "fr_sum.hip.h"
+// A tree has the shape of merkle_tree.hip.h, 64 bytes per node; a node without a right sibling is hashed with itself (the
+// reference's _build_tree).  Layout, build schedule and the gather of opening paths are that header's; this file brings the hash.
+// Workgroups of MLE_TILE threads on the capped strided grid of fr_sum.hip.h; plain C++, no atomics.
+#include "merkle_tree.hip.h"
 
 namespace zkmi {
 
-constexpr int MERKLE_MAX_LOG = ZK_MERKLE_MAX_LOG;
-constexpr uint64_t MERKLE_MAX_LEAVES = 1ull << MERKLE_MAX_LOG;
 constexpr uint64_t DIGEST = ZK_MERKLE_DIGEST;
 constexpr int DIGEST_WORDS = 8;
 // ---- BLAKE2b ------------------------------------------------------------------------------------------------------------
@@ -186,48 +184,7 @@ __global__ __launch_bounds__(MLE_TILE) void merkle_level_kernel(uint64_t n_child
     for (uint64_t i = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; i < n_parent; i += stride) merkle_parent(child, n_child, i, parent);
 }
 
-struct MerkleLayout {
-    int depth;
-    uint64_t nodes;
-    uint64_t offset[MERKLE_MAX_LOG + 1];   // of level l, in nodes
-};
-
-static MerkleLayout merkle_layout(uint64_t n) {
-    MerkleLayout lay{};
-    uint64_t width = n;
-    for (;;) {
-        lay.offset[lay.depth] = lay.nodes;
-        lay.nodes += width;
-        if (width == 1) break;
-        width = (width + 1) / 2;
-        ++lay.depth;
-    }
-    return lay;
-}
-
-// entry (q, l) of the paths of k queries into a tree of n leaves: the sibling of query q's ancestor at level l, the ancestor
-// itself where it has none.  An index past the leaves opens the last leaf.
-__global__ __launch_bounds__(MLE_TILE) void merkle_paths_kernel(uint64_t n, MerkleLayout lay, const uint8_t* __restrict__ tree, uint64_t k,
-                                                                const uint64_t* __restrict__ indices, uint8_t* __restrict__ paths) {
-    const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE, depth = (uint64_t)lay.depth, items = k * depth;
-    for (uint64_t e = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; e < items; e += stride) {
-        const uint64_t q = e / depth, l = e - q * depth;
-        const uint64_t width = (n + (1ull << l) - 1) >> l, idx = umin64(indices[q], n - 1) >> l;
-        const uint64_t sib = (idx ^ 1) < width ? idx ^ 1 : idx;
-        uint64_t w[DIGEST_WORDS];
-        node_load(tree + (lay.offset[l] + sib) * DIGEST, w);
-        node_store(paths + e * DIGEST, w);
-    }
-}
-
 // ---- host side ----------------------------------------------------------------------------------------------------------
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static int leaves_in_range(uint64_t n, const char* who) {
-    if (n == 0 || n > MERKLE_MAX_LEAVES) return fail(ZK_ERR_ARG, std::string(who) + ": need 1 <= n <= 2^26");
-    return ZK_OK;
-}
 
 static int blake2b_rows(uint64_t n, const void* d_rows, uint64_t row_bytes, void* d_digests, hipStream_t st) {
     ZK_HIP_RC(leaves_in_range(n, "blake2b_rows"));
@@ -261,39 +218,10 @@ static int blake2b_items(uint64_t n, const void* d_data, uint64_t data_bytes, co
 }
 
 static int merkle_build(uint64_t n, void* d_tree, hipStream_t st) {
-    ZK_HIP_RC(leaves_in_range(n, "merkle_build"));
-    if (!d_tree) return fail(ZK_ERR_ARG, "merkle_build: null tree");
-    if (!aligned16(d_tree)) return fail(ZK_ERR_ARG, "merkle_build: the tree starts at a multiple of 16");
-    uint8_t* level = (uint8_t*)d_tree;
-    // one launch per level, down to the root's single lane: one workgroup that finishes the narrow levels behind barriers was
-    // measured and did not beat the launches it replaces (EXPERIMENTS.md "Merkle trees")
-    for (uint64_t width = n; width > 1; width = (width + 1) / 2) {
-        uint8_t* parent = level + width * DIGEST;
-        hipLaunchKernelGGL(merkle_level_kernel, dim3(fr_blocks((width + 1) / 2)), dim3(MLE_TILE), 0, st, width, (const uint8_t*)level, parent);
-        ZK_HIP(hipGetLastError());
-        level = parent;
-    }
-    return ZK_OK;
-}
-
-static int merkle_paths(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices, void* d_paths, hipStream_t st) {
-    ZK_HIP_RC(leaves_in_range(n, "merkle_paths"));
-    if (!d_tree) return fail(ZK_ERR_ARG, "merkle_paths: null tree");
-    if (k == 0) return ZK_OK;
-    if (k > (1ull << 32)) return fail(ZK_ERR_ARG, "merkle_paths: at most 2^32 queries a call");
-    if (!d_indices || !d_paths) return fail(ZK_ERR_ARG, "merkle_paths: null pointer");
-    if (!aligned16(d_tree) || !aligned16(d_paths) || ((uintptr_t)d_indices & 7))
-        return fail(ZK_ERR_ARG, "merkle_paths: tree and paths start at a multiple of 16, the indices at a multiple of 8");
-    const MerkleLayout lay = merkle_layout(n);
-    const uint64_t items = k * (uint64_t)lay.depth;
-    const void* in[2] = {d_tree, d_indices};
-    const uint64_t len[2] = {lay.nodes * DIGEST, k * 8};
-    if (overlaps_any(d_paths, items * DIGEST, in, len, 2)) return fail(ZK_ERR_ARG, "merkle_paths: the paths overlap an input");
-    if (items == 0) return ZK_OK;   // one leaf: the root is the leaf's digest and a path is empty
-    hipLaunchKernelGGL(merkle_paths_kernel, dim3(fr_blocks(items)), dim3(MLE_TILE), 0, st, n, lay, (const uint8_t*)d_tree, k,
-                       (const uint64_t*)d_indices, (uint8_t*)d_paths);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
+    ZK_HIP_RC(tree_build_args("merkle_build", n, d_tree));
+    return tree_build<DIGEST>(n, d_tree, [st](uint64_t width, const uint8_t* child, uint8_t* parent) {
+        hipLaunchKernelGGL(merkle_level_kernel, dim3(fr_blocks((width + 1) / 2)), dim3(MLE_TILE), 0, st, width, child, parent);
+    });
 }
 
 }  // namespace zkmi
@@ -312,7 +240,7 @@ int zk_blake2b_items_dev(uint64_t n, const void* d_data, uint64_t data_bytes, co
 
 int zk_merkle_layout(uint64_t n, int* depth, uint64_t* level_offset, uint64_t* nodes) {
     ZK_HIP_RC(leaves_in_range(n, "merkle_layout"));
-    const MerkleLayout lay = merkle_layout(n);
+    const TreeLayout lay = tree_layout(n);
     if (depth) *depth = lay.depth;
     if (nodes) *nodes = lay.nodes;
     if (level_offset)
@@ -323,7 +251,7 @@ int zk_merkle_layout(uint64_t n, int* depth, uint64_t* level_offset, uint64_t* n
 int zk_merkle_build_dev(uint64_t n, void* d_tree, void* stream) { return merkle_build(n, d_tree, (hipStream_t)stream); }
 
 int zk_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices, void* d_paths, void* stream) {
-    return merkle_paths(n, d_tree, k, d_indices, d_paths, (hipStream_t)stream);
+    return tree_paths<DIGEST>("merkle_paths", n, d_tree, k, d_indices, d_paths, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // poseidon.hip -- the Poseidon permutation over BN254 Fr / BLS12-381 Fr, the fixed-length hash, a sponge over rows and Merkle
-// trees of 32-byte nodes (gfx950).  DESIGN.md section 4.15 fixes the definitions.
+// trees of 32-byte nodes (gfx950).  DESIGN.md section 4.15 fixes the definitions; the tree apart from its hash (layout, build
+// schedule, opening paths) is merkle_tree.hip.h.
 //
 // The reference has no algebraic hash: its only Poseidon is the circom fixture its Groth16 test proves (tests/stub/test_poseidon.*),
 // and that fixture is what pins width 4 here.  Poseidon (Grassi et al., USENIX Security 2021) with S-box x^5, R_F = 8 and circomlib's
@@ -13,12 +14,10 @@
 // threads on the capped strided grid of fr_sum.hip.h; plain C++, no atomics, no LDS.
 #include <mutex>
 #include <vector>
-#include "fr_sum.hip.h"
+#include "merkle_tree.hip.h"
 
 namespace zkmi {
 
-constexpr int POSEIDON_MAX_LOG = ZK_POSEIDON_MAX_LOG;
-constexpr uint64_t POSEIDON_MAX_ITEMS = 1ull << POSEIDON_MAX_LOG;
 constexpr uint64_t POSEIDON_MAX_ROW = ZK_POSEIDON_MAX_ROW;
 constexpr uint64_t NODE = 32;       // bytes per tree node: one canonical Fr element
 constexpr int POSEIDON_RF = 8;
@@ -183,42 +182,6 @@ __global__ __launch_bounds__(MLE_TILE) void poseidon_level_kernel(uint64_t n_chi
     }
 }
 
-struct PoseidonLayout {
-    int depth;
-    uint64_t nodes;
-    uint64_t offset[POSEIDON_MAX_LOG + 1];   // of level l, in nodes
-};
-
-// the levels of zk_merkle_layout
-static PoseidonLayout poseidon_layout(uint64_t n) {
-    PoseidonLayout lay{};
-    uint64_t width = n;
-    for (;;) {
-        lay.offset[lay.depth] = lay.nodes;
-        lay.nodes += width;
-        if (width == 1) break;
-        width = (width + 1) / 2;
-        ++lay.depth;
-    }
-    return lay;
-}
-
-// entry (q, l) of the paths of k queries into a tree of n leaves: the sibling of query q's ancestor at level l, the ancestor
-// itself where it has none.  An index past the leaves opens the last leaf.  A node is two 16-byte accesses.
-__global__ __launch_bounds__(MLE_TILE) void poseidon_paths_kernel(uint64_t n, PoseidonLayout lay, const uint4* __restrict__ tree, uint64_t k,
-                                                                  const uint64_t* __restrict__ indices, uint4* __restrict__ paths) {
-    const uint64_t stride = (uint64_t)gridDim.x * MLE_TILE, depth = (uint64_t)lay.depth, items = k * depth;
-    for (uint64_t e = (uint64_t)blockIdx.x * MLE_TILE + threadIdx.x; e < items; e += stride) {
-        const uint64_t q = e / depth, l = e - q * depth;
-        const uint64_t width = (n + (1ull << l) - 1) >> l, last = n - 1, want = indices[q];
-        const uint64_t idx = (want < last ? want : last) >> l;
-        const uint64_t sib = (idx ^ 1) < width ? idx ^ 1 : idx;
-        const uint4 lo = tree[(lay.offset[l] + sib) * 2], hi = tree[(lay.offset[l] + sib) * 2 + 1];
-        paths[e * 2] = lo;
-        paths[e * 2 + 1] = hi;
-    }
-}
-
 // ---- parameters: the paper's Grain LFSR on the host ---------------------------------------------------------------------------
 
 // 80 bits, b[0] the oldest; update: new = b62 ^ b51 ^ b38 ^ b23 ^ b13 ^ b0, shift, append
@@ -338,12 +301,6 @@ static PoseidonTables g_poseidon;
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
-static bool poseidon_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static int poseidon_items_in_range(uint64_t n, const char* who) {
-    if (n == 0 || n > POSEIDON_MAX_ITEMS) return fail(ZK_ERR_ARG, std::string(who) + ": need 1 <= n <= 2^26");
-    return ZK_OK;
-}
 static int poseidon_curve_ok(int curve, const char* who) {
     if (curve != ZK_CURVE_BN254 && curve != ZK_CURVE_BLS12_381) return fail(ZK_ERR_ARG, std::string(who) + ": unknown curve");
     return ZK_OK;
@@ -353,7 +310,7 @@ static_assert(ZK_CURVE_BN254 == 0 && ZK_CURVE_BLS12_381 == 1, "PoseidonTables is
 // `n_in` elements at d_in and `n_out` at d_out, both present and at multiples of 16; they overlap only as d_out == d_in where that is allowed
 static int poseidon_spans_ok(const void* d_in, uint64_t n_in, const void* d_out, uint64_t n_out, bool in_place, const char* who) {
     if (!d_in || !d_out) return fail(ZK_ERR_ARG, std::string(who) + ": null pointer");
-    if (!poseidon_aligned16(d_in) || !poseidon_aligned16(d_out)) return fail(ZK_ERR_ARG, std::string(who) + ": vectors start at a multiple of 16");
+    if (!aligned16(d_in) || !aligned16(d_out)) return fail(ZK_ERR_ARG, std::string(who) + ": vectors start at a multiple of 16");
     if (in_place && d_in == d_out) return ZK_OK;
     if (ranges_overlap(d_out, n_out * NODE, d_in, n_in * NODE)) return fail(ZK_ERR_ARG, std::string(who) + ": the output overlaps the input");
     return ZK_OK;
@@ -393,36 +350,10 @@ static int poseidon_build_impl(int curve, uint64_t n, void* d_tree, hipStream_t 
     if (n == 1) return ZK_OK;   // one leaf is its own root
     const uint32_t* tab = nullptr;
     ZK_HIP_RC(g_poseidon.get<P>(curve, 3, &tab));
-    uint8_t* level = (uint8_t*)d_tree;
-    // one launch per level down to the root's single lane, merkle.hip's schedule (EXPERIMENTS.md "Merkle trees")
-    for (uint64_t width = n; width > 1; width = (width + 1) / 2) {
-        uint8_t* parent = level + width * NODE;
-        hipLaunchKernelGGL(poseidon_level_kernel<P>, dim3(fr_blocks((width + 1) / 2)), dim3(MLE_TILE), 0, st, width, tab, (const uint32_t*)level,
+    return tree_build<NODE>(n, d_tree, [=](uint64_t width, const uint8_t* child, uint8_t* parent) {
+        hipLaunchKernelGGL(poseidon_level_kernel<P>, dim3(fr_blocks((width + 1) / 2)), dim3(MLE_TILE), 0, st, width, tab, (const uint32_t*)child,
                            (uint32_t*)parent);
-        ZK_HIP(hipGetLastError());
-        level = parent;
-    }
-    return ZK_OK;
-}
-
-static int poseidon_paths(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices, void* d_paths, hipStream_t st) {
-    ZK_HIP_RC(poseidon_items_in_range(n, "poseidon_merkle_paths"));
-    if (!d_tree) return fail(ZK_ERR_ARG, "poseidon_merkle_paths: null tree");
-    if (k == 0) return ZK_OK;
-    if (k > (1ull << 32)) return fail(ZK_ERR_ARG, "poseidon_merkle_paths: at most 2^32 queries a call");
-    if (!d_indices || !d_paths) return fail(ZK_ERR_ARG, "poseidon_merkle_paths: null pointer");
-    if (!poseidon_aligned16(d_tree) || !poseidon_aligned16(d_paths) || ((uintptr_t)d_indices & 7))
-        return fail(ZK_ERR_ARG, "poseidon_merkle_paths: tree and paths start at a multiple of 16, the indices at a multiple of 8");
-    const PoseidonLayout lay = poseidon_layout(n);
-    const uint64_t items = k * (uint64_t)lay.depth;
-    const void* in[2] = {d_tree, d_indices};
-    const uint64_t len[2] = {lay.nodes * NODE, k * 8};
-    if (overlaps_any(d_paths, items * NODE, in, len, 2)) return fail(ZK_ERR_ARG, "poseidon_merkle_paths: the paths overlap an input");
-    if (items == 0) return ZK_OK;   // one leaf: the root is the leaf's digest and a path is empty
-    hipLaunchKernelGGL(poseidon_paths_kernel, dim3(fr_blocks(items)), dim3(MLE_TILE), 0, st, n, lay, (const uint4*)d_tree, k, (const uint64_t*)d_indices,
-                       (uint4*)d_paths);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
+    });
 }
 
 // CALL(P, T) for the (curve, t) pair; both have been checked
@@ -459,7 +390,7 @@ int zk_poseidon_params(int curve, int t, int* rf, int* rp, uint64_t* out) {
 int zk_poseidon_perm_dev(int curve, int t, uint64_t n, const void* d_in, void* d_out, void* stream) {
     ZK_HIP_RC(poseidon_curve_ok(curve, "poseidon_perm"));
     if (t < 3 || t > 5) return fail(ZK_ERR_ARG, "poseidon_perm: the state has 3, 4 or 5 elements");
-    ZK_HIP_RC(poseidon_items_in_range(n, "poseidon_perm"));
+    ZK_HIP_RC(leaves_in_range(n, "poseidon_perm"));
     ZK_HIP_RC(poseidon_spans_ok(d_in, n * t, d_out, n * t, true, "poseidon_perm"));
 #define CALL(P, T) return poseidon_perm_impl<P, T>(curve, n, d_in, d_out, (hipStream_t)stream)
     ZK_DISPATCH_POSEIDON(curve, t, CALL);
@@ -469,7 +400,7 @@ int zk_poseidon_perm_dev(int curve, int t, uint64_t n, const void* d_in, void* d
 int zk_poseidon_hash_dev(int curve, int k, uint64_t n, const void* d_rows, void* d_out, void* stream) {
     ZK_HIP_RC(poseidon_curve_ok(curve, "poseidon_hash"));
     if (k < 2 || k > 4) return fail(ZK_ERR_ARG, "poseidon_hash: a row has 2, 3 or 4 elements");
-    ZK_HIP_RC(poseidon_items_in_range(n, "poseidon_hash"));
+    ZK_HIP_RC(leaves_in_range(n, "poseidon_hash"));
     ZK_HIP_RC(poseidon_spans_ok(d_rows, n * k, d_out, n, false, "poseidon_hash"));
 #define CALL(P, T) return poseidon_hash_impl<P, T>(curve, n, d_rows, d_out, (hipStream_t)stream)
     ZK_DISPATCH_POSEIDON(curve, k + 1, CALL);
@@ -478,7 +409,7 @@ int zk_poseidon_hash_dev(int curve, int k, uint64_t n, const void* d_rows, void*
 
 int zk_poseidon_sponge_rows_dev(int curve, uint64_t n, const void* d_rows, uint64_t row_elems, void* d_digests, void* stream) {
     ZK_HIP_RC(poseidon_curve_ok(curve, "poseidon_sponge_rows"));
-    ZK_HIP_RC(poseidon_items_in_range(n, "poseidon_sponge_rows"));
+    ZK_HIP_RC(leaves_in_range(n, "poseidon_sponge_rows"));
     if (row_elems == 0 || row_elems > POSEIDON_MAX_ROW) return fail(ZK_ERR_ARG, "poseidon_sponge_rows: a row has 1 to 2^20 elements");
     ZK_HIP_RC(poseidon_spans_ok(d_rows, n * row_elems, d_digests, n, false, "poseidon_sponge_rows"));
 #define CALL(P) return poseidon_sponge_impl<P>(curve, n, d_rows, row_elems, d_digests, (hipStream_t)stream)
@@ -488,16 +419,14 @@ int zk_poseidon_sponge_rows_dev(int curve, uint64_t n, const void* d_rows, uint6
 
 int zk_poseidon_merkle_build_dev(int curve, uint64_t n, void* d_tree, void* stream) {
     ZK_HIP_RC(poseidon_curve_ok(curve, "poseidon_merkle_build"));
-    ZK_HIP_RC(poseidon_items_in_range(n, "poseidon_merkle_build"));
-    if (!d_tree) return fail(ZK_ERR_ARG, "poseidon_merkle_build: null tree");
-    if (!poseidon_aligned16(d_tree)) return fail(ZK_ERR_ARG, "poseidon_merkle_build: the tree starts at a multiple of 16");
+    ZK_HIP_RC(tree_build_args("poseidon_merkle_build", n, d_tree));
 #define CALL(P) return poseidon_build_impl<P>(curve, n, d_tree, (hipStream_t)stream)
     ZK_DISPATCH_FR(curve, CALL);
 #undef CALL
 }
 
 int zk_poseidon_merkle_paths_dev(uint64_t n, const void* d_tree, uint64_t k, const void* d_indices, void* d_paths, void* stream) {
-    return poseidon_paths(n, d_tree, k, d_indices, d_paths, (hipStream_t)stream);
+    return tree_paths<NODE>("poseidon_merkle_paths", n, d_tree, k, d_indices, d_paths, (hipStream_t)stream);
 }
 
 // the hook of host.hip (zk_shutdown)
