@@ -703,6 +703,35 @@ int zk_gkr_phase2_dev(int curve, int log_rows, uint64_t n_entries, const void* d
 int zk_gkr_wiring_eval_dev(int curve, uint64_t n_gates, const void* d_types, const void* d_in1, const void* d_in2, int log_a,
                            const void* d_er, int log_prev, const void* d_eu, const void* d_ev, uint64_t* out, void* stream);
 
+/* ---- Spartan over R1CS: witness products and row binding (csrc/spartan.hip) ------------------------------------------------
+ * Both entry points walk a MERGED THREE-MATRIX CSR with n_seg = 2^log_seg segments, 0 <= log_seg <= ZK_R1CS_MAX_LOG:
+ * ptr u32[3 n_seg + 1]; sub-segment q = 3 i + m holds the entries of matrix m (0 A, 1 B, 2 C) in segment i, at
+ * idx[ptr[q] .. ptr[q+1]) (u32) and val (canonical Fr); n_entries = ptr[3 n_seg] < 2^32.  Padding segments are empty; a repeated
+ * (segment, idx) adds.  x is a table of 2^log_x canonical Fr elements and THE CALLER has checked idx < 2^log_x (Spartan's
+ * constructor does): the kernels gather x[idx[k]] without a bounds test.  Per segment acc_m = sum_k val[k] x[idx[k]] over
+ * sub-segment 3 i + m: one product per entry.
+ * Long segments -- those with a sub-segment of more than ZK_R1CS_LONG_ROW entries: long_segs u32[n_long] (ascending segment
+ * indices), item_ptr u32[3 n_long + 1] into items (the items of sub-segment m of long segment j are item_ptr[3 j + m] ..
+ * item_ptr[3 j + m + 1]: none for a short sub-segment), items u32[n_items][2] = entry ranges [k0, k1) as spmv.py's long_row_items
+ * cuts them from ptr, d_partials = n_items elements of scratch.  With n_long = 0 (and then n_items = 0) these four may be NULL.
+ * Sums are fixed-order (exact and repeatable); no atomics; every output element is written once, empty sub-segments as zero.
+ * ZK_ERR_ARG for a null pointer, log_seg or log_x out of range, n_entries >= 2^32, n_long > n_items, n_items > n_entries,
+ * n_long > 2^log_seg, n_items without n_long, a missing long-segment array, or an output (d_partials included) that overlaps
+ * another buffer of the call; nothing is written then.  Both enqueue only. */
+#define ZK_R1CS_MAX_LOG 24
+#define ZK_R1CS_LONG_ROW 64
+/* The row-major CSR (segments = constraints, idx = column, x = z): d_az[i], d_bz[i], d_cz[i] = acc_A, acc_B, acc_C for every
+ * i < 2^log_seg -- A z, B z and C z from one pass over one index stream. */
+int zk_r1cs_products_dev(int curve, int log_seg, uint64_t n_entries, const void* d_ptr, const void* d_idx, const void* d_val,
+                         uint64_t n_long, const void* d_long_segs, const void* d_item_ptr, uint64_t n_items, const void* d_items,
+                         void* d_partials, int log_x, const void* d_z, void* d_az, void* d_bz, void* d_cz, void* stream);
+/* The column-major CSR (segments = columns, idx = constraint, x = E = eq(rx, .)): d_out[y] = cA acc_A + cB acc_B + cC acc_C =
+ * sum_i E[i] (cA A + cB B + cC C)[i, y] for every y < 2^log_seg.  coeff: cA, cB, cC, 3 x 4 limbs in host memory, reduced on
+ * entry.  One product per entry and three per segment. */
+int zk_r1cs_bind_dev(int curve, int log_seg, uint64_t n_entries, const void* d_ptr, const void* d_idx, const void* d_val,
+                     uint64_t n_long, const void* d_long_segs, const void* d_item_ptr, uint64_t n_items, const void* d_items,
+                     void* d_partials, int log_x, const void* d_e, const uint64_t* coeff, void* d_out, void* stream);
+
 /* Dense-polynomial helpers over Fr used by the PlonK prover (python/zksnake/plonk/protocol.py:157-484); canonical
  * coefficients, lowest degree first, host memory.  They replace Polynomial.__call__ (src/bn254/polynomial.rs:491-516),
  * Polynomial.__truediv__ by a linear factor (:404-438), the batch_modinv + accumulator loop of protocol.py:296-307 and

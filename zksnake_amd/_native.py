@@ -49,6 +49,8 @@ POSEIDON_MAX_ROW = 1 << 20  # ZK_POSEIDON_MAX_ROW: elements per row of the Posei
 FRI_MAX_LOG = 26  # ZK_FRI_MAX_LOG: a FRI layer has at most 2^26 elements
 GKR_MAX_LOG = 24  # ZK_GKR_MAX_LOG: a layer of a GKR circuit has at most 2^24 wires
 GKR_LONG_ROW = 64  # ZK_GKR_LONG_ROW: CSR rows with more entries leave the lane-per-row kernel of the GKR passes
+R1CS_MAX_LOG = 24  # ZK_R1CS_MAX_LOG: a merged R1CS CSR has at most 2^24 segments, and the table it gathers from 2^24 elements
+R1CS_LONG_ROW = 64  # ZK_R1CS_LONG_ROW: sub-segments with more entries make their segment a long one
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -172,6 +174,8 @@ SIGNATURES = {
     "zk_gkr_phase1_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "zk_gkr_phase2_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "zk_gkr_wiring_eval_dev": (_i, [_i, _u64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _u64p, _vp]),
+    "zk_r1cs_products_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "zk_r1cs_bind_dev": (_i, [_i, _i, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _i, _vp, _u64p, _vp, _vp]),
     "zk_fr_poly_eval": (_i, [_i, _u64, _u64p, _u64p, _u64p]),
     "zk_fr_poly_div_linear": (_i, [_i, _u64, _u64p, _u64p, _u64p, _u64p]),
     "zk_fr_grand_product": (_i, [_i, _u64, _u64p, _u64p, _u64p]),
